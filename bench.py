@@ -13,8 +13,10 @@ inside a step, ONE RCCL all_gather of the per-env returns at the end of the roll
 parent -- and fails non-zero unless exactly N ranks join; under torchrun (WORLD_SIZE set) it is one of the ranks.
 
 Inputs (actions, counter-based stream keyed by the global env id) are generated on the device before the timed region.
-At N=1 the line also carries `extra`: the same kernels on workloads where robots move and fall (share of env-substeps
-that leave the packed fast path included), configs[2] (OSC controller in the loop) and configs[4] (Cassie3d).
+A plain run measures the headline and nothing else.  `--full` adds what takes runs of its own: at N=1 `extra` (the same
+kernels on workloads where robots move and fall -- share of env-substeps that leave the packed fast path included --,
+configs[2] (OSC controller in the loop), configs[4] (Cassie3d), the TRPO outer loop) and `cpu_baseline`; at N>1 the TRPO
+outer loop on the sharded envs.  `--dump-outputs DIR` writes what the last timed Env.step returned (DIR/<name>.npy).
 """
 import argparse
 import json
@@ -70,13 +72,19 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=150)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--no-trpo", action="store_true", help="N > 1: skip the TRPO outer loop (configs[3]'s caller) after the random-policy rollout")
+    ap.add_argument("--full", action="store_true", help="also measure what is not the headline: N = 1: the other workloads (`extra`) and the CPU "
+                                                       "baselines; N > 1: the TRPO outer loop (configs[3]'s caller) after the random-policy rollout")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the arrays the last timed Env.step returned (and the gathered returns) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N = 1: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full, N = 1: skip the other workloads")
+    ap.add_argument("--no-trpo", action="store_true", help="--full, N > 1: skip the TRPO outer loop")
     ap.add_argument("--trpo-iters", type=int, default=6)
     ap.add_argument("--trpo-timeout", type=float, default=300.0, help="N > 1: seconds after which a TRPO stage that has not finished is taken for a lost rank (headline printed, exit 6)")
     ap.add_argument("--cpu-legs-only", action="store_true", help="internal: print the CPU legs of configs[0]/[2]/[4] as JSON (no GPU) and exit")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.envs_per_gpu < 1:
+        ap.error("--steps and --envs-per-gpu must be positive, --warmup not negative")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ launcher (no GPU call)
@@ -709,6 +717,27 @@ def roofline_object(n_local, kernel_ms, dominant, pmc):
                     "HBM-bound (hbm.frac)"}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every array as out_dir/<name>.npy (float32 / float64).  Row i is environment i.  If the arrays hold more than DUMP_BYTES
+    together, a fixed sample of rows (seed 0, the same for every array of the same length) is written instead, with the environment index
+    of each row in <name>_rows.npy: two runs with the same arguments write the same rows."""
+    total = sum(a.nbytes for a in arrays.values())
+    room = DUMP_BYTES - 2 * 1024 * len(arrays)   # (.npy headers of an array and its row index)
+    keep = 1.0 if total <= room else room / (total + 8 * sum(len(a) for a in arrays.values()))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if keep < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), max(1, int(len(a) * keep)), replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ one rank
 def worker(args):
     import torch
@@ -797,6 +826,10 @@ def worker(args):
     kernel_ms = kev0.elapsed_time(kev1) / args.steps
     q, v = env.get_state_host()
     finite = bool(np.isfinite(q).all() and np.isfinite(v).all())
+    # what the last timed Env.step returned to its caller (this rank's envs), its state records' qpos / qvel, and the returns the collective gathered
+    outputs = None if not (args.dump_outputs and rank == 0) else dict(obs=out["obs"].cpu().numpy(), reward=out["reward"].cpu().numpy(),
+                                                      done=out["done"].cpu().numpy().astype(np.float32), qpos=q, qvel=v,
+                                                      returns=all_returns.cpu().numpy())
     tier = env.tier_info()   # what the library chose for this handle (batch size, flags, CASSIE2D_* overrides), not a re-derivation of its rule
     env.close()
     backend = R.dist.get_backend() if R.dist.is_initialized() else None
@@ -834,9 +867,11 @@ def worker(args):
             "episodes_terminated_per_env_step": float(dones.item()) / (n_local * args.steps),
             "cleanup_frac": counters["cleanup_frac"], "k1_frac": counters["k1_frac"], "nonfinite_resets": counters["nonfinite_resets"],
             "workload_note": "reference quirk Q3 (stale qstate) makes reward < 0.6 on every step, so every env terminates and auto-resets "
-                             "each step: the headline is the reference-faithful but degenerate regime; `extra` holds the regimes where robots move",
+                             "each step: the headline is the reference-faithful but degenerate regime; `extra` (--full) holds the regimes where robots move",
             "cpu_baseline": None,
         }
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
 
     def print_line():
         # RCCL writes its banner ("Librccl path : ...") through C stdio, which is flushed at exit when stdout is a pipe: flush
@@ -853,7 +888,7 @@ def worker(args):
     # above stays the headline metric and is ALREADY in `line`: if the ranks fall out of step inside this stage, rank 0 prints the
     # headline with the reason and every rank exits non-zero (trpo_outer_loop: on_desync).
     trpo_row = None
-    if world > 1 and not args.no_trpo:
+    if world > 1 and args.full and not args.no_trpo:
         def on_desync(reason):
             if rank == 0:
                 line["config"]["trpo_outer_loop"] = dict(workload="trpo_outer_loop_walk_pd", error=reason)
@@ -867,7 +902,7 @@ def worker(args):
         if trpo_row is not None:
             line["config"]["trpo_outer_loop"] = trpo_row
             line["config"]["trpo_outer_loop_env_steps_per_s"] = trpo_row.get("env_steps_per_s")
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             try:
                 line["extra"] = extra_workloads(traj, n_local)
                 # the regimes where robots move, fall and lie on the ground, where the driver's record keeps them (env-steps/s)
@@ -876,7 +911,7 @@ def worker(args):
                 line["config"]["trpo_outer_loop_env_steps_per_s"] = line["config"]["env_steps_per_s_other_workloads"].get("trpo_outer_loop_walk_pd")
             except Exception as ex:  # the headline stays valid; say what failed
                 line["extra"] = [{"error": repr(ex)}]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
             # two CPU legs on this box's host cores: the SAME SOURCE as the HIP kernel through its host backend (the fair one), and
             # the oracle (dense 3-D O(n^3) restatement, the parity checker)

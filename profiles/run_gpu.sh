@@ -15,7 +15,7 @@ for w in $what; do
       tail -5 "$out/pytest_gpu.log"
       [ -f "$root/gpurun_out/fullsize.jsonl" ] && cp "$root/gpurun_out/fullsize.jsonl" "$out/fullsize.jsonl" ;;
     bench)
-      timeout 900 python3 bench.py > "$out/bench.json" 2> "$out/bench.err"; echo "bench rc=$?"
+      timeout 900 python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err"; echo "bench rc=$?"
       tail -c 3000 "$out/bench.json" ;;
     prof)
       ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o bench -- \

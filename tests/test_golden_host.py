@@ -61,9 +61,13 @@ def test_trajectory_lookup_semantics(kat, traj):
         assert np.array_equal(tr.state(t)[0], q)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/rllab/trajectory/stepdata.bin"), reason="reference data only in the build container")
-def test_trajectory_conversion_from_stepdata(traj):
-    tr = Cassie2dTraj("/root/reference/rllab/trajectory/stepdata.bin")
+def test_trajectory_conversion_from_stepdata(traj, tmp_path):
+    # tests/golden/stepdata.bin.xz: the reference's rllab/trajectory/stepdata.bin, byte for byte, xz-compressed
+    import lzma
+    path = tmp_path / "stepdata.bin"
+    with lzma.open(os.path.join(GOLDEN, "stepdata.bin.xz")) as f:
+        path.write_bytes(f.read())
+    tr = Cassie2dTraj(str(path))
     assert np.array_equal(tr.time, traj["time"])
     np.testing.assert_allclose(tr.qpos, traj["qpos"], rtol=0, atol=1e-15)
     assert np.array_equal(tr.qvel, traj["qvel"]) and np.array_equal(tr.torque, traj["torque"])

@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -51,9 +52,10 @@ def _free_port():
 
 
 def test_bench_line_contract_small():
-    rc, out, err = _run(["--steps", "6", "--warmup", "2", "--envs-per-gpu", "2048", "--no-cpu-baseline", "--no-extra"])
+    rc, out, err = _run(["--steps", "6", "--warmup", "2", "--envs-per-gpu", "2048"])
     assert rc == 0, err[-2000:]
     line = _line(out)
+    assert "extra" not in line and line["cpu_baseline"] is None   # a plain run measures the headline alone (the rest: --full)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in line, k
@@ -65,6 +67,28 @@ def test_bench_line_contract_small():
     assert abs(r["hbm"]["achieved"] - 905 * 2048 / (r["kernel_ms"] * 1e-3) / 1e9) < 1e-9 * r["hbm"]["achieved"]
     assert abs(line["value"] - 2048 * 6 / (line["ms_per_step"] * 6e-3)) < 1e-6 * line["value"]
     assert line["episodes_terminated_per_env_step"] == 1.0  # quirk Q3: the reference-faithful walk env ends every step
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: what the last timed Env.step returned, as float32 / float64 .npy files, the same from run to run with the same
+    arguments; the returns are the ones behind the line's checksum."""
+    args = ["--steps", "5", "--warmup", "1", "--envs-per-gpu", "2048"]
+    dumps = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        rc, out, err = _run(args + ["--dump-outputs", str(d)])
+        assert rc == 0, err[-2000:]
+        line = _line(out)
+        assert line["steps"] == 5
+        dumps.append({f.stem: np.load(f) for f in d.glob("*.npy")})
+    a, b = dumps
+    shapes = {"obs": (2048, 26), "reward": (2048,), "done": (2048,), "qpos": (2048, 13), "qvel": (2048, 13), "returns": (2048,)}
+    assert {k: v.shape for k, v in a.items()} == shapes
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    for k in shapes:
+        assert np.array_equal(a[k], b[k]), k
+    assert np.isfinite(a["obs"]).all() and set(np.unique(a["done"])) <= {0.0, 1.0}
+    assert abs(a["returns"].sum() - line["returns_checksum"]) <= 1e-9 * abs(line["returns_checksum"])
 
 
 def test_rccl_gather_with_a_forced_single_rank_process_group():
@@ -80,7 +104,7 @@ def test_gpus_n_spawns_n_ranks_or_fails_loudly():
     """`python bench.py --gpus 2` without torchrun: on a box with >= 2 GPUs two NCCL ranks must join (n_gpus == 2 in the line);
     on a 1-GPU box the launcher must refuse with a non-zero exit code instead of silently reporting one rank."""
     import torch
-    rc, out, err = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--envs-per-gpu", "1024", "--no-cpu-baseline"])
+    rc, out, err = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--envs-per-gpu", "1024", "--full", "--no-cpu-baseline"])
     if torch.cuda.device_count() >= 2:
         assert rc == 0, err[-2000:]
         line = _line(out)
@@ -94,7 +118,7 @@ def test_two_ranks_sharing_one_gpu_exercise_the_n_rank_path():
     there: the self-spawning launcher, the rendezvous, global env ids per shard, the gather and the max-over-ranks timing --
     with both ranks mapped to device 0 and gloo carrying the two collectives (test hooks CASSIE_DEVICE_MAP / CASSIE_BACKEND)."""
     env = dict(CASSIE_DEVICE_MAP="0,0", CASSIE_BACKEND="gloo")
-    rc, out, err = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--envs-per-gpu", "2048", "--no-cpu-baseline", "--trpo-iters", "2"], env)
+    rc, out, err = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--envs-per-gpu", "2048", "--full", "--no-cpu-baseline", "--trpo-iters", "2"], env)
     assert rc == 0, err[-2000:]
     line = _line(out)
     assert line["n_gpus"] == 2 and line["config"]["envs_total"] == 4096 and line["finite"] and "extra" not in line
@@ -124,7 +148,7 @@ def test_bench_under_torchrun_as_the_driver_launches_it():
     import signal
     env = dict(os.environ, CASSIE_DEVICE_MAP="0,0", CASSIE_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--envs-per-gpu", "2048", "--no-cpu-baseline", "--trpo-iters", "2"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--envs-per-gpu", "2048", "--full", "--no-cpu-baseline", "--trpo-iters", "2"]
     p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
     try:
         out, err = p.communicate(timeout=600)
@@ -153,7 +177,7 @@ def test_configs3_eight_ranks_of_65536_envs_on_one_gpu():
     shards: their checksum equals ONE rank stepping the same 524 288 global env ids.  What remains untested afterwards is RCCL
     with N > 1 alone."""
     env = dict(CASSIE_DEVICE_MAP="0,0,0,0,0,0,0,0", CASSIE_BACKEND="gloo")
-    rc, out, err = _run(["--gpus", "8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], env, timeout=2400)
+    rc, out, err = _run(["--gpus", "8", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], env, timeout=2400)
     assert rc == 0, err[-2000:]
     line = _line(out)
     assert line["n_gpus"] == 8 and line["config"]["envs_per_gpu"] == 65536 and line["config"]["envs_total"] == 524288
@@ -182,7 +206,7 @@ def test_trpo_stage_is_skipped_on_every_rank_when_one_cannot_construct_it():
     the others waiting in a broadcast.  Rank 1 is made to fail its construction: the ranks agree (all_reduce MIN) to skip, the run ends with rc 0,
     ONE JSON line, the headline measured before the stage intact and the row saying why it was skipped."""
     env = dict(CASSIE_DEVICE_MAP="0,0", CASSIE_BACKEND="gloo", CASSIE_TEST_HOOKS="1", CASSIE_TEST_TRPO_FAIL_RANK="1")
-    rc, out, err = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "2048", "--no-cpu-baseline", "--trpo-iters", "2", "--trpo-timeout", "60"], env, timeout=150, attempts=1)
+    rc, out, err = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "2048", "--full", "--no-cpu-baseline", "--trpo-iters", "2", "--trpo-timeout", "60"], env, timeout=150, attempts=1)
     assert rc == 0, err[-2000:]
     line = _line(out)
     assert sum(1 for l in out.splitlines() if l.startswith("{")) == 1
@@ -197,7 +221,7 @@ def test_headline_survives_a_rank_that_dies_inside_the_trpo_stage():
     import time
     env = dict(CASSIE_DEVICE_MAP="0,0", CASSIE_BACKEND="gloo", CASSIE_TEST_HOOKS="1", CASSIE_TEST_TRPO_DIE_RANK="1")
     t0 = time.time()
-    rc, out, err = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "2048", "--no-cpu-baseline", "--trpo-iters", "2", "--trpo-timeout", "60"], env,
+    rc, out, err = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "2048", "--full", "--no-cpu-baseline", "--trpo-iters", "2", "--trpo-timeout", "60"], env,
                         timeout=150, attempts=1)
     assert rc != 0 and rc != 124 and time.time() - t0 < 120, (rc, err[-1500:])
     line = _line(out)

@@ -20,9 +20,9 @@ def png():
 
 def test_png_reader_against_the_fixture(png, tmp_path):
     gray, name = png
-    ref = os.path.join("/root/reference/model/terrains", name)
-    if os.path.exists(ref):  # build container only; the fixture itself was cross-checked against a second decoder when it was made
-        assert np.array_equal(T.read_png_gray(ref), gray)
+    # the reference's terrain image the fixture was decoded from, stored beside it (the fixture itself was cross-checked against a
+    # second decoder when it was made)
+    assert np.array_equal(T.read_png_gray(os.path.join(GOLDEN, name)), gray)
     # a PNG written here with every filter type exercises Sub / Up / Average / Paeth without the reference tree
     import struct
     import zlib
