@@ -19,7 +19,7 @@ EXPORTS = [
     "GetOperationalSpaceState", "Display", "Render",
     # batched ABI (include/cassie_vec.h)
     "CassieVecCreate", "CassieVecFree", "CassieVecLastError", "CassieVecNumEnvs", "CassieVecActionDim",
-    "CassieVecSetStream", "CassieVecSynchronize", "CassieVecGetCounters", "CassieVecResetCounters", "CassieVecTierInfo", "CassieVecQpIterations", "CassieVecSetTrajectory", "CassieVecSetHeightField", "CassieVecReset", "CassieVecResetTo",
+    "CassieVecSetStream", "CassieVecSynchronize", "CassieVecGetCounters", "CassieVecResetCounters", "CassieVecTierInfo", "CassieVecQpIterations", "CassieVecSetTrajectory", "CassieVecSetHeightField", "CassieVecSetTerrainLibrary", "CassieVecSetTerrainIds", "CassieVecGetTerrainIds", "CassieVecReset", "CassieVecResetTo",
     "CassieVecStep", "CassieVecSubstep", "CassieVecStandingStep", "CassieVecAccumulate", "CassieVecGetState", "CassieVecGetOpState", "CassieVecStatePtr",
     "CassieVecStepHost", "CassieVecGetStateHost", "CassieVecSetStateHost", "CassieVecGetFullStateHost",
     "CassieVecDebugSubstepHost", "CassieVecDebugWorkspaceHost", "CassieVecTimeSteps",
@@ -73,6 +73,10 @@ def load():
         L.CassieVecTierInfo.argtypes = [vp, ct.POINTER(ct.c_uint64)]
     L.CassieVecSetTrajectory.argtypes = [vp, dp, dp, ct.c_int]
     L.CassieVecSetHeightField.argtypes = [vp, dp, ct.c_int, ct.c_int, ct.c_double, ct.c_double]
+    if hasattr(L, "CassieVecSetTerrainLibrary"):   # (absent from A/B libraries built from earlier sources: CASSIE2D_LIB)
+        L.CassieVecSetTerrainLibrary.argtypes = [vp, ct.c_int, vp, vp, vp, dp]
+        L.CassieVecSetTerrainIds.argtypes = [vp, u8p, vp]
+        L.CassieVecGetTerrainIds.argtypes = [vp, vp]
     L.CassieVecReset.argtypes = [vp, u8p, dp]
     L.CassieVecResetTo.argtypes = [vp, u8p, dp, dp, dp]
     L.CassieVecStep.argtypes = [vp, dp, dp, dp, u8p, dp]

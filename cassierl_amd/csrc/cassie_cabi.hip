@@ -36,7 +36,12 @@ struct CassieVec {
   double* traj_qpos = nullptr;
   double traj_tmax = 0.0;
   int traj_n = 0;
-  cassie::Terrain hf{};  // device height field (N4) or {null}
+  // terrain library (N4): the fields' heights back to back, one descriptor per field, the field of every environment; hf_n == 0: the flat floor
+  double* hf_heights = nullptr;
+  cassie::Terrain* hf_fields = nullptr;
+  int hf_n = 0;
+  int* hf_ids = nullptr;                     // [n] device, in [0, hf_n) (allocated with the first library; CassieVecSetTerrainIds checks before it writes)
+  int* hf_bad = nullptr;                     // device word of that check
   // scratch for the host-pointer conveniences
   double *d_act = nullptr, *d_obs = nullptr, *d_rew = nullptr, *d_q = nullptr, *d_v = nullptr, *d_dbg = nullptr;
   double *ovf = nullptr, *ovf_dbg = nullptr;  // workspace for constraint columns beyond the register-resident ones
@@ -124,7 +129,9 @@ cassie::VecParams make_params(CassieVec* h) {
   p.ovf_stride = OVF_STRIDE;
   p.stats = h->stats;
   p.qp_stats = h->qp_stats;
-  p.hf = h->hf;
+  p.hf.fields = h->hf_n ? h->hf_fields : nullptr;
+  p.hf.ids = h->hf_ids;
+  p.hf.n_fields = h->hf_n;
   p.phase = h->phase;
   return p;
 }
@@ -165,6 +172,7 @@ void launch_first_tier(CassieVec* h, int mode, const cassie::VecParams& p, bool 
       if (p.terminal_obs) q.terminal_obs = p.terminal_obs + o * 26;
       if (p.reward) q.reward = p.reward + o;
       if (p.done) q.done = p.done + o;
+      if (p.hf.ids) q.hf.ids = p.hf.ids + o;
     }
     if (hf) L2::step_leg_hf(mode, h->n - nd, h->stream, q, h->pending_leg + nd); else L2::step_leg(mode, h->n - nd, h->stream, q, h->pending_leg + nd);
   }
@@ -322,7 +330,7 @@ int launch_ctrl_step(CassieVec* h, int mode, const cassie::VecParams& p, const d
       ps.n_sub = 1;
       if (sub != p.n_sub - 1) { ps.obs = nullptr; ps.terminal_obs = nullptr; }
       L2::ctrl_g16(ctrl, scripted, h->n, h->stream, ps, zpos, zvel);
-      if (h->hf.h) {
+      if (h->hf_n) {
         launch_physics_tiers_hf(h, 2, ps);
       } else {
         launch_physics_tiers(h, 2, ps);
@@ -336,7 +344,7 @@ int launch_ctrl_step(CassieVec* h, int mode, const cassie::VecParams& p, const d
       if (sub != p.n_sub - 1) { ps.obs = nullptr; ps.terminal_obs = nullptr; }
       L2::ctrl_k4(ctrl, scripted, h->n, h->stream, ps, zpos, zvel);
       ps.debug = nullptr;
-      if (h->hf.h) L2::step_k1_hf(2, h->n, h->stream, ps);
+      if (h->hf_n) L2::step_k1_hf(2, h->n, h->stream, ps);
       else L2::step_k1(2, L2::K1_DEEP, h->n, h->stream, ps);
     }
   }
@@ -346,7 +354,7 @@ int launch_ctrl_step(CassieVec* h, int mode, const cassie::VecParams& p, const d
 
 int launch_step(CassieVec* h, int mode, const cassie::VecParams& p) {
   const bool pdtq = mode == CASSIE_CTRL_PD || mode == CASSIE_CTRL_TORQUE;
-  if (h->hf.h) {
+  if (h->hf_n) {
     // height-field terrain: the 4-environments-per-wavefront and wave-per-environment kernels with the terrain collision stage
     if (!pdtq) return launch_ctrl_step(h, mode, p, nullptr, nullptr);
     if (p.debug) return fail(h, CASSIE_EINVAL, "the debug substep has no height-field variant");
@@ -382,7 +390,7 @@ int launch_reset(CassieVec* h, const uint8_t* mask, const double* q, const doubl
     L2::get_state(h->n, h->stream, h->state, h->d_q, h->d_v);
     q = h->d_q; v = h->d_v;
   }
-  if (h->hf.h) L2::reset_hf(h->n, h->stream, p, mask, q, v);
+  if (h->hf_n) L2::reset_hf(h->n, h->stream, p, mask, q, v);
   else if (h->g16 && h->reset_packed && h->need_slow) {
     // two lanes per environment, 32 environments per wavefront; a state with more than 8 rows on a leg is left to the
     // wave-per-environment kernel through the mask the packed kernel writes
@@ -501,7 +509,7 @@ int CassieVecCreate(CassieVec** out, int n_envs, int device, const CassieVecConf
 void CassieVecFree(CassieVec* h) {
   if (!h) return;
   hipSetDevice(h->device);
-  hipFree(h->state); hipFree(h->traj_qpos); hipFree((void*)h->hf.h); hipFree(h->d_act); hipFree(h->d_obs); hipFree(h->d_rew);
+  hipFree(h->state); hipFree(h->traj_qpos); hipFree(h->hf_heights); hipFree(h->hf_fields); hipFree(h->hf_ids); hipFree(h->hf_bad); hipFree(h->d_act); hipFree(h->d_obs); hipFree(h->d_rew);
   hipFree(h->d_done); hipFree(h->d_q); hipFree(h->d_v); hipFree(h->d_dbg); hipFree(h->ovf); hipFree(h->ovf_dbg); hipFree(h->pending); hipFree(h->pending_leg); hipFree(h->duo_ws); hipFree(h->qp_stats); hipFree(h->pend_count); hipFree(h->stats); hipFree(h->phase);
   if (h->ev0) hipEventDestroy(h->ev0);
   if (h->ev1) hipEventDestroy(h->ev1);
@@ -627,20 +635,70 @@ int CassieVecSetTrajectory(CassieVec* h, const double* time_host, const double* 
   return CASSIE_OK;
 }
 
+int CassieVecSetTerrainLibrary(CassieVec* h, int n_fields, const int* nrow, const int* ncol, const double (*size_xy)[2], const double* heights_host) {
+  if (!h) return CASSIE_EINVAL;
+  if (n_fields < 0 || (n_fields > 0 && (!nrow || !ncol || !size_xy || !heights_host))) return fail(h, CASSIE_EINVAL, "bad terrain library");
+  size_t total = 0;
+  for (int k = 0; k < n_fields; k++) {
+    if (nrow[k] < 2 || ncol[k] < 2 || !(size_xy[k][0] > 0) || !(size_xy[k][1] > 0)) return fail(h, CASSIE_EINVAL, "bad height field %d of the terrain library", k);
+    total += (size_t)nrow[k] * ncol[k];
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // no launch in flight reads the library this call replaces
+  hipFree(h->hf_heights); hipFree(h->hf_fields);
+  h->hf_heights = nullptr; h->hf_fields = nullptr; h->hf_n = 0;
+  if (n_fields == 0) return CASSIE_OK;   // back to the flat floor
+  std::vector<cassie::Terrain> desc(n_fields);
+  HIPCHK(h, hipMalloc(&h->hf_heights, total * sizeof(double)));
+  HIPCHK(h, hipMemcpy(h->hf_heights, heights_host, total * sizeof(double), hipMemcpyHostToDevice));
+  size_t off = 0;
+  for (int k = 0; k < n_fields; k++) {
+    const size_t cnt = (size_t)nrow[k] * ncol[k];
+    double hmax = heights_host[off];
+    for (size_t i = 1; i < cnt; i++) hmax = heights_host[off + i] > hmax ? heights_host[off + i] : hmax;
+    desc[k].h = h->hf_heights + off; desc[k].nrow = nrow[k]; desc[k].ncol = ncol[k];
+    desc[k].sx = size_xy[k][0]; desc[k].sy = size_xy[k][1]; desc[k].hmax = hmax;
+    off += cnt;
+  }
+  HIPCHK(h, hipMalloc(&h->hf_fields, n_fields * sizeof(cassie::Terrain)));
+  HIPCHK(h, hipMemcpy(h->hf_fields, desc.data(), n_fields * sizeof(cassie::Terrain), hipMemcpyHostToDevice));
+  if (!h->hf_ids) HIPCHK(h, hipMalloc(&h->hf_ids, (size_t)h->n * sizeof(int)));
+  HIPCHK(h, hipMemsetAsync(h->hf_ids, 0, (size_t)h->n * sizeof(int), h->stream));   // every environment on field 0
+  h->hf_n = n_fields;
+  return CASSIE_OK;
+}
+
 int CassieVecSetHeightField(CassieVec* h, const double* heights_host, int nrow, int ncol, double size_x, double size_y) {
   if (!h) return CASSIE_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->hf.h) { hipFree((void*)h->hf.h); h->hf = cassie::Terrain{}; }
-  if (!heights_host) return CASSIE_OK;  // back to the flat floor
+  const int rc = CassieVecSetTerrainLibrary(h, 0, nullptr, nullptr, nullptr, nullptr);   // the field goes first, whatever follows
+  if (rc != CASSIE_OK || !heights_host) return rc;                                       // NULL: back to the flat floor
   if (nrow < 2 || ncol < 2 || !(size_x > 0) || !(size_y > 0)) return fail(h, CASSIE_EINVAL, "bad height field");
-  double* d = nullptr;
-  const size_t bytes = (size_t)nrow * ncol * sizeof(double);
-  HIPCHK(h, hipMalloc(&d, bytes));
-  HIPCHK(h, hipMemcpy(d, heights_host, bytes, hipMemcpyHostToDevice));
-  double hmax = heights_host[0];
-  for (size_t i = 1; i < (size_t)nrow * ncol; i++) hmax = heights_host[i] > hmax ? heights_host[i] : hmax;
-  h->hf.h = d; h->hf.nrow = nrow; h->hf.ncol = ncol; h->hf.sx = size_x; h->hf.sy = size_y; h->hf.hmax = hmax;
+  const double size_xy[1][2] = {{size_x, size_y}};
+  return CassieVecSetTerrainLibrary(h, 1, &nrow, &ncol, size_xy, heights_host);   // a library of one
+}
+
+int CassieVecSetTerrainIds(CassieVec* h, const uint8_t* mask_dev, const int* ids_dev) {
+  if (!h || !ids_dev) return fail(h, CASSIE_EINVAL, "ids_dev is required");
+  if (!h->hf_n) return fail(h, CASSIE_EINVAL, "no terrain library is set");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!h->hf_bad) HIPCHK(h, hipMalloc(&h->hf_bad, sizeof(int)));
+  int bad = 0;
+  HIPCHK(h, hipMemsetAsync(h->hf_bad, 0, sizeof(int), h->stream));
+  L2::terrain_ids_check(h->n, h->stream, ids_dev, mask_dev, h->hf_n, h->hf_bad);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(&bad, h->hf_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // the one synchronisation of this call: the range check decides whether anything is written
+  if (bad) return fail(h, CASSIE_EINVAL, "terrain id outside [0, %d): the assignment is unchanged", h->hf_n);
+  L2::terrain_ids_set(h->n, h->stream, h->hf_ids, ids_dev, mask_dev);
+  HIPCHK(h, hipGetLastError());
+  return CASSIE_OK;
+}
+
+int CassieVecGetTerrainIds(CassieVec* h, int* ids_dev) {
+  if (!h || !ids_dev) return fail(h, CASSIE_EINVAL, "ids_dev is required");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->hf_n) HIPCHK(h, hipMemcpyAsync(ids_dev, h->hf_ids, (size_t)h->n * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+  else HIPCHK(h, hipMemsetAsync(ids_dev, 0, (size_t)h->n * sizeof(int), h->stream));   // the flat floor: every id reads 0
   return CASSIE_OK;
 }
 

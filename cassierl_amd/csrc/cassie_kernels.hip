@@ -175,7 +175,12 @@ __device__ __forceinline__ double impedance(double d0, double d1, double width, 
 }
 
 // height-field terrain (N4): terrain_sphere() -- the sphere against the closest feature of the terrain's sagittal section -- lives in
-// cassie_terrain.h (shared with the other kernel families and the CPU instantiation of the two-lanes-per-environment core)
+// cassie_terrain.h (shared with the other kernel families and the CPU instantiation of the two-lanes-per-environment core).
+// The field of an environment: its entry of the batch's terrain library (terrain_of); the flat-floor instantiations get null and never read it.
+template <bool HF> __device__ __forceinline__ const Terrain* terrain_env(const VecParams& p, int env) {
+  if constexpr (HF) return &terrain_of(p.hf, env);
+  else return nullptr;
+}
 
 // ---------------------------------------------------------------- planar forward kinematics on the link lanes
 // Reads sm.q/sm.v-like arrays (qsrc, vsrc), writes link arrays.  SEM selects the model semantics table.
@@ -917,7 +922,7 @@ __global__ void __launch_bounds__(64, WPS) env_step_kernel(VecParams p) {
       ctrl = act_l;
     }
     lds_sync();
-    substep<true, MAXACT, HF>(sm, c, lane, ctrl, so, dbg, ovf, &p.hf);
+    substep<true, MAXACT, HF>(sm, c, lane, ctrl, so, dbg, ovf, terrain_env<HF>(p, env));
     niter_sum += so.niter;
     time += 0.0005;
     if (sub == n_sub - 1 && c.dvalid && c.grp == 0 && c.act >= 0) sm.ctrl[c.act] = ctrl;  // mj_data->ctrl
@@ -953,7 +958,7 @@ __global__ void __launch_bounds__(64, WPS) env_step_kernel(VecParams p) {
       time = 0.0;
       wset_keep = 0.0;  // new episode: cold start of the OSC QP too
       lds_sync();
-      substep<false, MAXACT, HF>(sm, c, lane, c.act >= 0 ? sm.ctrl[c.act] : 0.0, so, nullptr, ovf, &p.hf);
+      substep<false, MAXACT, HF>(sm, c, lane, c.act >= 0 ? sm.ctrl[c.act] : 0.0, so, nullptr, ovf, terrain_env<HF>(p, env));
       opstate18(sm, c, lane, fix_kin, s18);
       sp = 0.0;
       if (lane < 17) sp = s18[lane + 1];
@@ -990,7 +995,7 @@ __global__ void __launch_bounds__(64) env_reset_kernel(VecParams p, const uint8_
   lds_sync();
   double qstate_l = (lane >= 1 && lane < 14) ? sm.q[lane - 1] : 0.0;
   StepOut so;
-  substep<false, 32, HF>(sm, c, lane, c.act >= 0 ? sm.ctrl[c.act] : 0.0, so, nullptr, p.ovf + (size_t)env * p.ovf_stride, &p.hf);
+  substep<false, 32, HF>(sm, c, lane, c.act >= 0 ? sm.ctrl[c.act] : 0.0, so, nullptr, p.ovf + (size_t)env * p.ovf_stride, terrain_env<HF>(p, env));
   if (p.obs) {
     opstate18(sm, c, lane, (p.flags & FLAG_FIX_STALE_KIN) != 0, s18);
     double sp = 0.0;

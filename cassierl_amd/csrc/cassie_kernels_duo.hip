@@ -328,6 +328,14 @@ struct DevDuoBHF : DevDuoB {
   struct Lds : DevDuoB::Lds {
     DuoSharedHF* shf;
     double a2[2];
+    // the batch's terrain library: ids of this wavefront's 64 environments (from fid0) and how many of them exist -- wave-uniform, so
+    // scalar registers; the set-up serves two groups per lane, so the environment is the GROUP's (g), not the lane's
+    const int* fid0;
+    int fid_n, n_fields;
+    LEG_FN const Terrain& terrain(const Terrain* lib) const {
+      const int e = g * 32 + (DUO_LANE >> 1);
+      return terrain_of(lib, fid0, n_fields, e < fid_n ? e : 0);
+    }
     LEG_FN double cld(int i) const { return i == 28 ? (g == 0 ? a2[0] : a2[1]) : DevDuoB::Lds::cld(i); }
     LEG_FN void cst(int i, double v, bool m) {
       if (i == 28) { if (m) { if (g == 0) a2[0] = v; else a2[1] = v; } }
@@ -387,12 +395,16 @@ __global__ void __launch_bounds__(64 * DUO_WAVES, 1) env_step_duo_hf_kernel(VecP
   lds.sh = &sh; lds.shf = &sh; lds.g = 0; lds.rec = p.state; lds.act = p.actions; lds.has_act = false; lds.snap = true;
   lds.lo = (lane & 1) * 5 + 3; lds.ao = (lane & 1) * 3;
   lds.a2[0] = 0.0; lds.a2[1] = 0.0;
+  {
+    const int w0 = wave_id * 64 < p.n_envs ? wave_id * 64 : 0;   // (a wavefront past the batch sets nothing up; its index stays in the array all the same)
+    lds.fid0 = p.hf.ids + w0; lds.fid_n = p.n_envs - w0; lds.n_fields = p.hf.n_fields;
+  }
   DevDuoBHF::W ws;
   const int slot = sl.claim(lane, wave_id, p.stats);   // (as env_step_duo_kernel)
   ws.r = __builtin_amdgcn_make_buffer_rsrc(workspace + (size_t)slot * duo_workspace_doubles_per_wave, 0, DDuoHF::W_N * 512, 0x00020000);
   ws.voff = (unsigned)lane * 16u;
   DDuoHF::Out o[2];
-  DDuoHF::env_step2<MODE, true>(cfg, lds, ws, io_of, valid, o, &p.hf);
+  DDuoHF::env_step2<MODE, true>(cfg, lds, ws, io_of, valid, o, p.hf.fields);
   sl.release(lane, slot);
 #pragma unroll
   for (int g = 0; g < 2; g++) {

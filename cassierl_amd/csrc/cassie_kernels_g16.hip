@@ -599,6 +599,10 @@ __global__ void __launch_bounds__(64, 2) env_step_g16_kernel(VecParams p, int* p
     const int ev = (int)blockIdx.x * 4 + (opaque((int)threadIdx.x) >> 4);
     return ev < p.n_envs ? (size_t)ev : 0;
   };
+  auto terrain_here = [&]() -> const Terrain* {   // the field of this group's environment (HF only: the flat floor evaluates nothing)
+    if constexpr (HF) return terrain_env<HF>(p, (int)env_again());
+    else return nullptr;
+  };
   PhaseClock pc;   // profiling builds only (-DCASSIE_PHASE_TIMING, tools/phase_profile.py physics)
   pc.start();
   LaneConst c;
@@ -637,7 +641,7 @@ __global__ void __launch_bounds__(64, 2) env_step_g16_kernel(VecParams p, int* p
     double cnew;
     if (reset_pass || MODE == 2) cnew = c.act >= 0 ? sm.ctrl[c.act] : 0.0;  // Cassie2d::Reset: mj_forward with the stale ctrl
     else { const double act_l = sm.actl[l]; cnew = MODE == 0 ? 10.0 * (act_l - q_d) + 5.0 * (0.0 - v_d) : act_l; }
-    substep<EnvLds, HF>(sm, c, l, g, cnew, reset_pass ? do_reset : (live && joined), !reset_pass, so, &p.hf, &pc);  // reset pose on the flat floor: 12 active rows
+    substep<EnvLds, HF>(sm, c, l, g, cnew, reset_pass ? do_reset : (live && joined), !reset_pass, so, terrain_here(), &pc);  // reset pose on the flat floor: 12 active rows
     if (!reset_pass) {
       if (live && joined && so.overflow) { live = false; pend = p.n_sub - sub; }  // hand the rest of this env to the clean-up pass
       if (live && joined) { sm.kq2[l] = q_d; sm.kv2[l] = v_d; sm.ctl[l] = cnew; niter_sum += so.niter; if (l == 0) sm.tim[0] += 0.0005; set_state = true; }  // setState of this substep

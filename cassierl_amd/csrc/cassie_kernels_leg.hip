@@ -234,19 +234,23 @@ __global__ void __launch_bounds__(64, 1) env_reset_leg_kernel(VecParams p, const
 // ---------------------------------------------------------------- height-field instantiation (tu_hf.hip)
 // The same core with the terrain collision stage (`terrain_sphere`, cassie_kernels.hip, which the including translation unit
 // provides): per contact pair one more per-lane LDS slot (the x component of the local terrain normal; nz = sqrt(1 - nx^2) > 0 for
-// a height field) -- 40.7 KB per wavefront, still four per CU.  A separate backend and kernel so that the flat-floor kernel above is
-// byte-for-byte what it was.
+// a height field) and the lane's field of the batch's terrain library (written once by the kernel, read by every collision stage:
+// `terrain`, cassie_leg_core.h) -- 40 960 B per wavefront, still four per CU.  A separate backend and kernel so that the flat-floor kernel
+// above is byte-for-byte what it was.
 struct DevBHF : DevB {
   struct Lds : DevB::Lds {
     double nrm[3][64];
+    int fid[64];   // field id of the lane's environment (terrain_id: already clamped to the library)
     LEG_FN void st_nrm(int slot, double nx, bool m) { if (m) nrm[slot][threadIdx.x] = nx; }
     LEG_FN double ld_nrm(int s) const { return nrm[s][threadIdx.x]; }
+    LEG_FN const Terrain& terrain(const Terrain* lib) const { return lib[fid[threadIdx.x]]; }
   };
   static LEG_FN void hf_sphere(const Terrain& t, double wx, double wy, double wz, double radius, double& dist, double& nx, double& nz) {
     cassie::terrain_sphere(t, wx, wy, wz, radius, dist, nx, nz);
   }
 };
 typedef Core<DevBHF> DCoreHF;
+static_assert(sizeof(DevBHF::Lds) <= 40960, "LDS budget of four wavefronts per CU");
 
 template <int MODE>
 __global__ void __launch_bounds__(64, 1) env_step_leg_hf_kernel(VecParams p, int* pending) {
@@ -267,8 +271,9 @@ __global__ void __launch_bounds__(64, 1) env_step_leg_hf_kernel(VecParams p, int
   io.tobs = p.terminal_obs + (io.has_tobs ? e * 26 : 0);
   io.rew = p.reward + (cfg.want_obs ? e : 0);
   io.done = p.done + (cfg.want_obs ? e : 0);
+  lds.fid[lane] = terrain_id(p.hf.ids, p.hf.n_fields, (int)e);
   DCoreHF::Out o;
-  DCoreHF::env_step<MODE, true>(cfg, lds, io, valid, o, &p.hf);
+  DCoreHF::env_step<MODE, true>(cfg, lds, io, valid, o, p.hf.fields);
   if (valid && (lane & 1) == 0) {
     pending[e] = o.pend;
     if (p.stats) {

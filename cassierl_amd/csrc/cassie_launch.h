@@ -21,10 +21,12 @@ constexpr int K1_HANDOVER_SPLIT = 8;  // workgroups that share the pending envir
 // tu_base.hip: wave-per-environment kernels (mode: 0 PD, 1 torque, 2 motor commands from the state record; K1_DEBUG: modes 0, 1)
 void step_k1(int mode, K1Variant variant, int n_envs, hipStream_t s, const VecParams& p, int split = 1);  // split: workgroups sharing the pending envs of a 64-block (hand-over pass)
 void reset(int n_envs, hipStream_t s, const VecParams& p, const uint8_t* mask, const double* qpos, const double* qvel);
-// tu_hf.hip: the same kernels with the height-field collision stage (p.hf.h != null); PD / torque modes
+// tu_hf.hip: the same kernels with the height-field collision stage (p.hf.fields != null: every environment on its field of the library)
 void step_k1_hf(int mode, int n_envs, hipStream_t s, const VecParams& p);
 void step_g16_hf(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending);
 void reset_hf(int n_envs, hipStream_t s, const VecParams& p, const uint8_t* mask, const double* qpos, const double* qvel);
+void terrain_ids_check(int n_envs, hipStream_t s, const int* ids, const uint8_t* mask, int n_fields, int* bad);   // bad[0] = 1: a selected id is outside [0, n_fields)
+void terrain_ids_set(int n_envs, hipStream_t s, int* dst, const int* ids, const uint8_t* mask);                    // dst[i] = ids[i] where mask (null: everywhere)
 void opstate(int n_envs, hipStream_t s, const VecParams& p, double* out18);
 void init_state(int n_envs, hipStream_t s, double* state);
 void get_state(int n_envs, hipStream_t s, const double* state, double* qpos, double* qvel);
@@ -40,7 +42,7 @@ void step_leg(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pend
 // table of table_slots busy words behind the workspaces, first probe = hash of its physical place (DuoSlots, cassie_kernels_duo.hip): the
 // workspace is sized by the chip, not by the batch.  flat_hint (tests): every wavefront starts probing at word 0.
 void step_duo(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending, double* workspace, int table_slots, bool flat_hint);
-void step_duo_hf(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending, double* workspace, int table_slots, bool flat_hint);   // tu_duo_hf.hip: ... on the height field (p.hf)
+void step_duo_hf(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending, double* workspace, int table_slots, bool flat_hint);   // tu_duo_hf.hip: ... on the terrain library (p.hf)
 int duo_table_slots(int n_envs, int simds);                  // 0 up to 1024 tasks, else a power of two >= 2 x simds
 int duo_workspace_slots_per_wave();                          // Duo::W_N: slots of 64 doubles per wavefront slot (diagnosis: CassieVecTierInfo)
 size_t duo_workspace_bytes(int n_envs, int table_slots);     // workspaces + claim table; to be zeroed once by the owner
@@ -51,7 +53,7 @@ void step_leg_segment(int mode, int n_envs, hipStream_t s, const VecParams& p, i
 void reset_leg(int n_envs, hipStream_t s, const VecParams& p, const uint8_t* mask, const double* qpos, const double* qvel, uint8_t* need_slow);
 // tags the pending environments the 4-envs-per-wave kernel could not hold either (PENDING_DEEP): they go straight to step_k1
 void classify_pending(int n_envs, hipStream_t s, const VecParams& p, int* pending);
-void step_leg_hf(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending);   // ... on the height field (p.hf)
+void step_leg_hf(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending);   // ... on the terrain library (p.hf)
 // tu_ctrl.hip / tu_ctrl_g16.hip: controllers (ctrl: 2 OSC, 3 Jacobian): they write the motor commands into the state record
 void ctrl_k4(int ctrl, bool scripted, int n_envs, hipStream_t s, const VecParams& p, const double* zpos, const double* zvel);
 // (the packed controller kernel only writes the motor commands; step_g16 / step_k1 with mode 2 then do the mj_step)

@@ -133,6 +133,12 @@ template <class B> struct Core {
   typedef typename B::K KP_;
   static LEG_FN D kc(KP_ K, int idx) { return B::kld(K, idx); }
 
+  // The height field under the lane's environment.  A backend whose Lds knows that environment's field provides
+  // `const Terrain& terrain(const Terrain* hf) const` (the device kernels: hf = the batch's library table, indexed by the environment's id);
+  // any other backend (the CPU instantiation of oracle/leg_host/) has one field under every environment: *hf.
+  template <class L> static LEG_FN auto terrain_for(const L& lds, const Terrain* hf, int) -> decltype(lds.terrain(hf)) { return lds.terrain(hf); }
+  template <class L> static LEG_FN const Terrain& terrain_for(const L&, const Terrain* hf, long) { return *hf; }
+
   // parent of leg link j (1..5) in the Kin numbering
   static constexpr int kparent(int j) { return j == 1 ? 0 : (j == 5 ? 1 : j - 1); }
 
@@ -494,7 +500,7 @@ template <class B> struct Core {
             const D basex = st.qb[0] - cp_qpos0[0] + cp_link_off[0][0][0];
             const D rad = c_sphr[Cc];
             D dist, nx, nz;
-            B::hf_sphere(*hf, basex + cx, c_sphy[Cc], basez + cz, rad, dist, nx, nz);
+            B::hf_sphere(terrain_for(lds, hf, 0), basex + cx, c_sphy[Cc], basez + cz, rad, dist, nx, nz);
             M act = dist < 0.0;
             if constexpr (Cc == 0) act = act & (leg == 0);
             const D back = rad + 0.5 * dist;

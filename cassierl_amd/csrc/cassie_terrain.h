@@ -32,6 +32,16 @@
 
 namespace cassie {
 
+// The field environment `env` stands on (a TerrainLib's table and ids).  Re-read at every collision stage from the small table (it stays
+// in cache), never held across a substep.  An id outside [0, n_fields) -- CassieVecSetTerrainIds never lets one through -- reads field 0:
+// no id value can make the collision stage read outside the library.
+CASSIE_TERRAIN_FN int terrain_id(const int* ids, int n_fields, int env) {
+  const int k = ids[env];
+  return (unsigned)k < (unsigned)n_fields ? k : 0;
+}
+CASSIE_TERRAIN_FN const Terrain& terrain_of(const Terrain* fields, const int* ids, int n_fields, int env) { return fields[terrain_id(ids, n_fields, env)]; }
+CASSIE_TERRAIN_FN const Terrain& terrain_of(const TerrainLib& lib, int env) { return terrain_of(lib.fields, lib.ids, lib.n_fields, env); }
+
 // squared distance from (cx, cz) to the segment (ax, az)-(bx, bz) and the closest point on it
 CASSIE_TERRAIN_FN void terrain_seg(double cx, double cz, double ax, double az, double bx, double bz, double& d2, double& qx, double& qz) {
   const double ux = bx - ax, uz = bz - az;

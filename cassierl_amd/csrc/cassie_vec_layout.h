@@ -56,6 +56,18 @@ struct Terrain {
   double hmax;   // largest height of the field: a sphere whose lowest point is above it touches nothing (early exit of terrain_sphere)
 };
 
+// The terrain under a batch: a library of height fields (one descriptor each, every field its own size and hmax) and the field of
+// every environment (CassieVecSetTerrainLibrary / CassieVecSetTerrainIds).  One field under everybody (CassieVecSetHeightField) is a
+// library of one with every id 0.  fields == null: the flat floor of the MJCF.  40 bytes, the size of the single descriptor this
+// replaced, so that the parameter block of the flat-floor kernels (which never read it) keeps its layout.
+struct TerrainLib {
+  const Terrain* fields;  // [n_fields] device
+  const int* ids;         // [n_envs] device, in [0, n_fields): checked when they are set, and clamped again where they are read (terrain_of)
+  int n_fields, unused_;
+  const void* reserved_[2];
+};
+static_assert(sizeof(TerrainLib) == sizeof(Terrain), "parameter block layout");
+
 struct VecParams {
   double* state;          // [n_envs][ENV_STRIDE]
   const double* actions;  // [n_envs][adim] device
@@ -75,7 +87,7 @@ struct VecParams {
   int serial;             // launch counter of the handle (scheduling hint only, see launch_physics_tiers)
   unsigned* pend_count;   // device [130]: [0] running sum of the current classify_pending launch, [1] arrival ticket of its sampling workgroups (both zero between launches), [2..65] per-serial sums, [66..129] their serials
   unsigned* pend_hint;    // host-visible [64]: estimated hand-overs of launch `serial` in word serial & 63 (classify_pending_kernel's last sampling workgroup stores the launch's total there: a plain store; scheduling hint only) or null
-  Terrain hf;             // terrain under the robots (PD / torque modes); hf.h == null: the flat floor of the MJCF
+  TerrainLib hf;          // terrain under the robots (the mj_step of every mode); hf.fields == null: the flat floor of the MJCF
   unsigned long long* phase;  // profiling builds only (-DCASSIE_PHASE_TIMING): [16] shader cycles accumulated per code phase
   unsigned* qp_stats;         // [3 n_envs] or null: per environment sum / maximum of the OSC QP's active-set iterations and StepOsc calls (CassieVecQpIterations)
   unsigned long long* stats;  // [STAT_N] event counters of this handle (rare-path atomics only), see STAT_*

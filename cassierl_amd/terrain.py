@@ -129,3 +129,63 @@ def height_at(heights_m, size_x, size_y, x, y):
     else:
         a, b = (z11 - z01) / dx, (z01 - z00) / dy
     return float(z00 + a * (fx * dx) + b * (fy * dy))
+
+
+# ---------------------------------------------------------------- a library of terrains, one per environment
+# terrain_random.py draws NUM_TERRAINS files from model/terrains/ per process, so each one-robot training run stands on different ground.
+# In a batch the same idea is a LIBRARY of fields (CassieVecEnv.set_terrain_library) and a field id per environment (set_terrain_ids).
+
+def library_from_pngs(paths, size=DEFAULT_SIZE):
+    """The fields of a terrain library from PNG files: hfield_from_png of each, all with the same <hfield> size."""
+    paths = list(paths)
+    if not paths:
+        raise ValueError("library_from_pngs: no files")
+    if len(size) < 3 or not (size[0] > 0 and size[1] > 0 and size[2] >= 0):
+        raise ValueError("library_from_pngs: size = (radius_x > 0, radius_y > 0, elevation_z >= 0[, base_z]), got %r" % (tuple(size),))
+    return [hfield_from_png(p, size) for p in paths]
+
+
+def assign_terrains(seed, global_env_ids, n_fields):
+    """Field id of each environment, uniform over [0, n_fields), keyed by (seed, GLOBAL env id) through rollout.counter_uniform: an
+    environment stands on the same terrain whichever rank owns it.  torch.int32 on the ids' device (what set_terrain_ids takes)."""
+    import torch
+    from .rollout import counter_uniform
+    n_fields = int(n_fields)
+    if n_fields <= 0:
+        raise ValueError("assign_terrains: n_fields must be positive, got %d" % n_fields)
+    ids = torch.as_tensor(global_env_ids, dtype=torch.int64)
+    if ids.ndim != 1:
+        raise ValueError("assign_terrains: global_env_ids must be one-dimensional")
+    u = counter_uniform(seed, ids, -1, 1)[:, 0]   # step -1: a stream no rollout draws from
+    return torch.clamp((u * n_fields).to(torch.int64), max=n_fields - 1).to(torch.int32)
+
+
+def clear_spawn(heights_m, size_x=10.0, size_y=10.0, x=(-0.2, 0.3), margin=1e-4):
+    """The field lowered so that the reset pose stands clear of it: the highest point under the feet's reach (x in the given range,
+    both legs' y) ends `margin` below the floor the pose was made for (spawn placement itself is not modelled)."""
+    hm = np.asarray(heights_m, dtype=np.float64)
+    top = max(height_at(hm, size_x, size_y, xx, y) for xx in np.linspace(x[0], x[1], 26) for y in (-0.1305, 0.1305))
+    return hm - top - margin
+
+
+def terrain_spec(terrain_dir, num_terrains, elevation, seed):
+    """A job's ground: K = num_terrains files drawn (terrain_random.py, with replacement) from terrain_dir with a generator seeded by
+    `seed`, their elevation (the <hfield> size_z) and the seed of the per-environment draw.  What a TRPO snapshot records."""
+    if not (elevation >= 0):
+        raise ValueError("terrain elevation must be >= 0, got %r" % (elevation,))
+    paths = choose_terrains(int(num_terrains), terrain_dir, np.random.default_rng(int(seed)))
+    return dict(dir=terrain_dir, files=[os.path.basename(p) for p in paths], elevation=float(elevation), seed=int(seed),
+                num_terrains=int(num_terrains))
+
+
+def spec_key(spec):
+    """The part of a terrain spec that decides the ground (not where the files live): compared on resume."""
+    return None if spec is None else dict(files=list(spec["files"]), elevation=float(spec["elevation"]), seed=int(spec["seed"]),
+                                          num_terrains=int(spec["num_terrains"]))
+
+
+def library_of_spec(spec):
+    """The fields of a spec, each lowered by clear_spawn so that the robots' reset pose stands clear of it."""
+    size = (DEFAULT_SIZE[0], DEFAULT_SIZE[1], spec["elevation"], DEFAULT_SIZE[3])
+    fields = library_from_pngs([os.path.join(spec["dir"], f) for f in spec["files"]], size)
+    return [clear_spawn(f, size[0], size[1]) for f in fields]

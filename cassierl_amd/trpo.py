@@ -20,6 +20,8 @@ import torch
 import torch.distributed as dist
 from torch import nn
 
+from . import terrain as terrain_lib
+
 
 # --------------------------------------------------------------------------------------------- distributed helpers
 def _world():
@@ -868,7 +870,8 @@ class TRPO:
                   baseline=None if self.baseline.coeffs is None else self.baseline.coeffs.detach().cpu(), itr=int(self.itr), extra=extra,
                   noise_step=int(self.noise_step), noise_seed=int(self.seed), gen_state=self.gen.get_state(), obs=None if self.obs is None else self.obs.cpu(),
                   path_t=self.path_t.cpu(), path_ret=self.path_ret.cpu(), steps_to_trunc=int(self._steps_to_trunc),
-                  env_state=None if env is None or not hasattr(env, "get_full_state_host") else torch.from_numpy(env.get_full_state_host()))
+                  env_state=None if env is None or not hasattr(env, "get_full_state_host") else torch.from_numpy(env.get_full_state_host()),
+                  terrain=terrain_lib.spec_key(getattr(self, "terrain_spec", None)))
         mine = self._rank_path(path)
         torch.save(ck, mine + ".tmp")
         os.replace(mine + ".tmp", mine)
@@ -881,6 +884,10 @@ class TRPO:
         dev = next(self.policy.parameters()).device
         mine = self._rank_path(path)
         ck = torch.load(mine if os.path.exists(mine) else path, map_location="cpu", weights_only=True)
+        # the ground is part of the run: resuming on other terrain would silently be a different run (snapshots without the key: flat floor)
+        mine_spec, theirs = terrain_lib.spec_key(getattr(self, "terrain_spec", None)), ck.get("terrain")
+        if mine_spec != theirs:
+            raise ValueError("TRPO.load: the snapshot was written on terrain %r, this job runs on %r" % (theirs, mine_spec))
         self.policy.load_state_dict(ck["policy"])
         self.baseline.coeffs = None if ck["baseline"] is None else ck["baseline"].to(dev)
         self.itr = ck["itr"]
@@ -913,10 +920,11 @@ def broadcast_initial_policy(algo):
         set_flat_params(algo.policy, theta)
 
 
-def make_cassie_trpo(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, sync_policy=True, **kw):
+def make_cassie_trpo(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, sync_policy=True, terrain=None, **kw):
     """trpo_cassie.py:12-42 on the batched MI355X environment.  sync_policy=False: NOTHING collective happens in here (the env, its workspaces, the
     policy are local allocations that can fail on one rank alone); the caller agrees on success across ranks first and then calls
-    broadcast_initial_policy(algo) (bench.py's TRPO stage)."""
+    broadcast_initial_policy(algo) (bench.py's TRPO stage).  terrain: None (the flat floor) or a spec of terrain.terrain_spec -- every
+    environment on its own field of the spec's library, drawn by terrain.assign_terrains over the GLOBAL env ids; snapshots record it."""
     from .vec_env import CassieVecEnv
     env = CassieVecEnv(n_envs, kind=kind, control_mode=control_mode, n_substeps=10, auto_reset=True, device=device, trajectory=trajectory)
     env.use_torch_stream()
@@ -929,6 +937,10 @@ def make_cassie_trpo(n_envs, kind="walk", control_mode="PD", device=0, trajector
     algo = TRPO(lambda a: env.step(a, bufs), lambda: env.reset(bufs), policy, LinearFeatureBaseline(), n_envs, obs_w, act_map, seed=seed,
                 env_reset_masked=lambda m: env.reset(bufs, mask=m), **kw)
     algo.env = env
+    algo.terrain_spec = terrain
+    if terrain is not None:
+        env.set_terrain_library(terrain_lib.library_of_spec(terrain), terrain_lib.DEFAULT_SIZE[:2])
+        env.set_terrain_ids(terrain_lib.assign_terrains(terrain["seed"], algo.env_ids, len(terrain["files"])).to(dev))
     if sync_policy:   # ... and rank 0's parameters are authoritative anyway
         broadcast_initial_policy(algo)
     return algo

@@ -100,6 +100,53 @@ class CassieVecEnv:
         assert hm.ndim == 2
         self._chk(self.L.CassieVecSetHeightField(self.h, hm.ctypes.data, hm.shape[0], hm.shape[1], float(size_x), float(size_y)))
 
+    def set_terrain_library(self, fields, sizes=(10.0, 10.0)):
+        """A library of height fields, one per environment (terrain_random.py's draw from model/terrains/, per environment of the
+        batch): `fields` = list of [nrow_k, ncol_k] height arrays in metres (each its own shape); `sizes` = one (size_x, size_y) for all,
+        or one pair per field.  Every environment starts on field 0 (set_terrain_ids moves it); an empty list restores the flat floor.
+        Environment i on field k computes, bit for bit, what it computes in a batch with set_heightfield(fields[k], *sizes[k])."""
+        fs = [np.ascontiguousarray(f, dtype=np.float64) for f in fields]
+        k = len(fs)
+        if k == 0:
+            self._chk(self.L.CassieVecSetTerrainLibrary(self.h, 0, None, None, None, None))
+            return
+        sz = np.asarray(sizes, dtype=np.float64)
+        sz = np.ascontiguousarray(np.broadcast_to(sz, (k, 2)) if sz.shape == (2,) else sz)
+        if sz.shape != (k, 2):
+            raise ValueError("sizes: one (size_x, size_y) pair, or one per field (%d); got shape %s" % (k, sz.shape))
+        for i, f in enumerate(fs):
+            if f.ndim != 2 or f.shape[0] < 2 or f.shape[1] < 2:
+                raise ValueError("field %d: a [nrow >= 2, ncol >= 2] height array, got shape %s" % (i, f.shape))
+        nrow = np.array([f.shape[0] for f in fs], dtype=np.int32)
+        ncol = np.array([f.shape[1] for f in fs], dtype=np.int32)
+        heights = np.ascontiguousarray(np.concatenate([f.ravel() for f in fs]))
+        self._chk(self.L.CassieVecSetTerrainLibrary(self.h, k, nrow.ctypes.data, ncol.ctypes.data, sz.ctypes.data, heights.ctypes.data))
+
+    def set_terrain_ids(self, ids, mask=None):
+        """Field of every environment (mask: bool / uint8 [n_envs] on the device, None = all): torch int32 [n_envs] on the device.
+        The ids are range-checked on the device (one synchronisation of the stream); an id outside the library raises and leaves the
+        assignment as it was.  Resets keep the ids: a new draw on `done` is a masked call."""
+        import torch
+        dev = torch.device("cuda:%d" % self.device)
+        ids = torch.as_tensor(ids, device=dev)
+        if ids.dtype != torch.int32 or ids.shape != (self.n_envs,):
+            raise ValueError("ids: torch.int32 [%d] on %s, got %s %s" % (self.n_envs, dev, ids.dtype, tuple(ids.shape)))
+        ids = ids.contiguous()
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask, device=dev)
+            if m.shape != (self.n_envs,):
+                raise ValueError("mask: [%d], got %s" % (self.n_envs, tuple(m.shape)))
+            m = m.to(torch.uint8).contiguous()
+        self._chk(self.L.CassieVecSetTerrainIds(self.h, None if m is None else m.data_ptr(), ids.data_ptr()))
+
+    def terrain_ids(self):
+        """torch int32 [n_envs] on the device: the field of every environment (0 everywhere on the flat floor)."""
+        import torch
+        out = torch.empty(self.n_envs, dtype=torch.int32, device="cuda:%d" % self.device)
+        self._chk(self.L.CassieVecGetTerrainIds(self.h, out.data_ptr()))
+        return out
+
     def synchronize(self):
         self._chk(self.L.CassieVecSynchronize(self.h))
 

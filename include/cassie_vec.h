@@ -107,9 +107,25 @@ int CassieVecSetTrajectory(CassieVec* h, const double* time_host, const double* 
 /* Height-field terrain under every robot of the batch (what rllab/envs/terrain_random.py:38-76 adds to the MJCF as
  * <hfield size="sx sy sz base" file=...> + <geom type="hfield">): heights_host[nrow][ncol] in METRES above the floor (row r at
  * y = -size_y + r * 2 size_y / (nrow - 1), column c likewise in x; host pointer, copied once).  NULL restores the flat floor.
- * With a field set only PD / torque modes step (CassieVecStep / CassieVecSubstep return CASSIE_EINVAL otherwise).
- * Collision model: sphere vs the triangle of the grid cell under its centre, in the robot's sagittal plane. */
+ * Every control mode steps on it: PD / torque directly, OSC / Jacobian through the mj_step behind their controllers (which, as in the
+ * reference, never see the contacts).  Collision model: the sphere against the closest feature of the terrain's cross-section in the
+ * robot's sagittal plane.  The same as a terrain library of one field with every id 0. */
 int CassieVecSetHeightField(CassieVec* h, const double* heights_host, int nrow, int ncol, double size_x, double size_y);
+
+/* A LIBRARY of height fields, one per environment (terrain_random.py draws its terrains from model/terrains/; in a batch every environment
+ * draws its own).  Field k: nrow[k] x ncol[k] heights in metres spanning [-size_xy[k][0], size_xy[k][0]] x [-size_xy[k][1], size_xy[k][1]],
+ * laid out as in CassieVecSetHeightField; the fields are concatenated row-major in heights_host (host arrays, copied once).  Sets every
+ * environment's id to 0.  n_fields == 0 restores the flat floor.  An environment's arithmetic on field k is bit-identical to the same
+ * environment in a batch that has CassieVecSetHeightField(field k). */
+int CassieVecSetTerrainLibrary(CassieVec* h, int n_fields, const int* nrow, const int* ncol, const double size_xy[][2], const double* heights_host);
+/* The field of every environment selected by mask_dev ([n] device, NULL = every environment): ids_dev[n] int32, device.  The ids are checked
+ * on the device against [0, n_fields): if any selected id is out of range the call returns CASSIE_EINVAL and the previous assignment stays in
+ * force.  That check costs ONE synchronisation of the handle's stream.  The ids belong to the handle, not to the state record: resets and
+ * auto-resets keep them; drawing new terrain for an environment is the caller's decision (e.g. a masked call on `done`).  CASSIE_EINVAL
+ * without a library. */
+int CassieVecSetTerrainIds(CassieVec* h, const uint8_t* mask_dev, const int32_t* ids_dev);
+/* ids_dev[n] int32, device <- the field of every environment (all 0 on the flat floor); stream-ordered, no synchronisation */
+int CassieVecGetTerrainIds(CassieVec* h, int32_t* ids_dev);
 
 /* masked reset to the Cassie2dEnv.reset pose; mask_dev == NULL resets every env; obs_dev may be NULL */
 int CassieVecReset(CassieVec* h, const uint8_t* mask_dev, double* obs_dev);

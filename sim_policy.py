@@ -25,12 +25,19 @@ def main():
     ap.add_argument("--control-mode", default="PD", choices=["PD", "Torque", "OSC"])
     ap.add_argument("--deterministic", action="store_true", help="act with the policy mean (no exploration noise)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--terrain-dir", default="", help="folder of terrain PNGs (model/terrains/ of the reference): robots on a terrain library")
+    ap.add_argument("--num-terrains", type=int, default=1, help="K fields drawn (with replacement) from --terrain-dir")
+    ap.add_argument("--terrain-elevation", type=float, default=1.0, help="height of a white pixel in metres (the <hfield> size_z)")
+    ap.add_argument("--terrain-seed", type=int, default=1, help="seed of the file draw and of the per-environment field ids")
     args = ap.parse_args()
     import torch
     from cassierl_amd import rollout as R
     from cassierl_amd.trajectory import default_gait
     from cassierl_amd.trpo import make_cassie_trpo
-    algo = make_cassie_trpo(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed)
+    from cassierl_amd.terrain import terrain_spec
+    terrain = terrain_spec(args.terrain_dir, args.num_terrains, args.terrain_elevation, args.terrain_seed) if args.terrain_dir else None
+    algo = make_cassie_trpo(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
+                            terrain=terrain)
     _, _ = algo.load(args.file, restore_sampler=False)   # policy + baseline only: every path starts from env.reset()
     pol, n = algo.policy, args.envs
     dt = next(pol.parameters()).dtype

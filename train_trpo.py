@@ -27,6 +27,10 @@ def main():
     ap.add_argument("--snapshot", default="")
     ap.add_argument("--load-policy", default="")
     ap.add_argument("--timing", action="store_true", help="report rollout / update seconds separately (adds synchronisations)")
+    ap.add_argument("--terrain-dir", default="", help="folder of terrain PNGs (model/terrains/ of the reference): robots on a terrain library")
+    ap.add_argument("--num-terrains", type=int, default=1, help="K fields drawn (with replacement) from --terrain-dir")
+    ap.add_argument("--terrain-elevation", type=float, default=1.0, help="height of a white pixel in metres (the <hfield> size_z)")
+    ap.add_argument("--terrain-seed", type=int, default=1, help="seed of the file draw and of the per-environment field ids")
     ap.add_argument("--dump-params", default="", help="rank 0 writes the flat policy parameters (.npy) after the last iteration")
     args = ap.parse_args()
     import torch
@@ -37,8 +41,10 @@ def main():
     dev = R.local_device(local_rank) if world > 1 else 0   # CASSIE_DEVICE_MAP (test hook): several ranks on one GPU
     torch.cuda.set_device(dev)
     traj = default_gait()
+    from cassierl_amd.terrain import terrain_spec
+    terrain = terrain_spec(args.terrain_dir, args.num_terrains, args.terrain_elevation, args.terrain_seed) if args.terrain_dir else None
     algo = make_cassie_trpo(args.envs_per_gpu, kind=args.kind, control_mode=args.control_mode, device=dev,
-                            trajectory=traj, seed=1, batch_size=args.envs_per_gpu * world * args.horizon)
+                            trajectory=traj, seed=1, batch_size=args.envs_per_gpu * world * args.horizon, terrain=terrain)
     algo.timing = args.timing
     if args.load_policy:
         _, restored = algo.load(args.load_policy)
