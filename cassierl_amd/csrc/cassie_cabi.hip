@@ -19,7 +19,28 @@
 #include "cassie3d_tables.h"
 #include "cassie_launch.h"
 
-namespace cassie { constexpr int NSLOT = CP_NSLOT; }
+namespace cassie {
+constexpr int NSLOT = CP_NSLOT;
+namespace launch {
+// the physics launchers (cassie_launch.h): the tier's height-field instantiation when the parameters carry a terrain library
+void step_k1(int mode, K1Variant variant, int n_envs, hipStream_t s, const VecParams& p, int split) {
+  (p.hf.fields ? step_k1_tier<true> : step_k1_tier<false>)(mode, variant, n_envs, s, p, split);
+}
+void reset(int n_envs, hipStream_t s, const VecParams& p, const uint8_t* mask, const double* qpos, const double* qvel) {
+  (p.hf.fields ? reset_tier<true> : reset_tier<false>)(n_envs, s, p, mask, qpos, qvel);
+}
+void step_g16(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending) {
+  (p.hf.fields ? step_g16_tier<true> : step_g16_tier<false>)(mode, n_envs, s, p, pending);
+}
+void step_leg(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending) {
+  (p.hf.fields ? step_leg_tier<true> : step_leg_tier<false>)(mode, n_envs, s, p, pending);
+}
+void step_duo(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending, double* workspace, int table_slots, bool flat_hint) {
+  (p.hf.fields ? step_duo_tier<true> : step_duo_tier<false>)(mode, n_envs, s, p, pending, workspace, table_slots, flat_hint);
+}
+}  // namespace launch
+}  // namespace cassie
+
 namespace L2 = cassie::launch;
 namespace L3 = cassie3d::launch;
 
@@ -155,12 +176,9 @@ bool seg_resources(CassieVec* h) {
 // The first tier of a launch (flat floor or height field): the first `duo_envs` environments in the 64-environments-per-wavefront kernel, the rest in
 // the two-lanes kernel (r06: a batch of whole rounds of the chip plus a remainder of at most one short round takes BOTH -- 65 537 .. 98 304 envs: 1.0 + 0.62 ms
 // instead of three short rounds; the two kernels are bit-identical, so which environment runs where is invisible in the results).
-void launch_first_tier(CassieVec* h, int mode, const cassie::VecParams& p, bool hf) {
+void launch_first_tier(CassieVec* h, int mode, const cassie::VecParams& p) {
   const int nd = h->duo_envs;
-  if (nd > 0) {
-    if (hf) L2::step_duo_hf(mode, nd, h->stream, p, h->pending_leg, h->duo_ws, h->duo_table, h->duo_flat_hint);
-    else L2::step_duo(mode, nd, h->stream, p, h->pending_leg, h->duo_ws, h->duo_table, h->duo_flat_hint);
-  }
+  if (nd > 0) L2::step_duo(mode, nd, h->stream, p, h->pending_leg, h->duo_ws, h->duo_table, h->duo_flat_hint);
   if (nd < h->n) {
     cassie::VecParams q = p;
     if (nd > 0) {   // the remainder: every per-environment array moved on by nd environments
@@ -174,21 +192,39 @@ void launch_first_tier(CassieVec* h, int mode, const cassie::VecParams& p, bool 
       if (p.done) q.done = p.done + o;
       if (p.hf.ids) q.hf.ids = p.hf.ids + o;
     }
-    if (hf) L2::step_leg_hf(mode, h->n - nd, h->stream, q, h->pending_leg + nd); else L2::step_leg(mode, h->n - nd, h->stream, q, h->pending_leg + nd);
+    L2::step_leg(mode, h->n - nd, h->stream, q, h->pending_leg + nd);
   }
 }
 
-// Physics tiers on the flat floor (mode 0 PD, 1 torque, 2 commands from the record).  Each tier leaves an environment it cannot
+// The tiers below the first, for the environments a first-tier launch left in `pend`: the deep ones (PENDING_DEEP, classify_pending) on stream
+// `sd` in the wave-per-environment kernel, the others on stream `ss` in the 4-environments-per-wavefront kernel and the wave-per-environment
+// pass behind it (what that passed on in `pend2`).  sd == ss: one after the other, the same kernels on the same data.
+void launch_lower_tiers(CassieVec* h, int mode, const cassie::VecParams& p, hipStream_t sd, hipStream_t ss, int* pend, int* pend2) {
+  cassie::VecParams pd = p, pa = p, pb = p;
+  pd.pending = pend; pd.pending_pick = cassie::PICK_DEEP;
+  L2::step_k1(mode, L2::K1_DEEP, h->n, sd, pd, L2::K1_HANDOVER_SPLIT);
+  pa.pending = pend; pa.pending_pick = cassie::PICK_SHALLOW;
+  L2::step_g16(mode, h->n, ss, pa, pend2);
+  pb.pending = pend2; pb.pending_pick = cassie::PICK_ALL;
+  L2::step_k1(mode, L2::K1_DEEP, h->n, ss, pb, L2::K1_HANDOVER_SPLIT);
+}
+
+// Physics tiers (mode 0 PD, 1 torque, 2 commands from the record).  Each tier leaves an environment it cannot
 // hold untouched from that substep on and says how many substeps are left; the next tier finishes it (results are what that
 // tier alone would give: an environment's arithmetic is a function of its own state in every kernel).
 //   tier 1  two lanes per environment (<= 8 rows per leg)        cassie_kernels_leg.hip   [h->leg]
 //   tier 2  four environments per wavefront (<= 16 rows)          cassie_kernels_g16.hip
 //   tier 3  one wavefront per environment (any number of rows)    cassie_kernels.hip
+// On the height field (p.hf.fields) always in the one-stream order at the end, without the hints (robots on terrain have not been profiled
+// lying down): the launch serial is not advanced, the hand-over ring is neither read nor cleared.
 void launch_physics_tiers(CassieVec* h, int mode, const cassie::VecParams& pin) {
   cassie::VecParams p = pin;
-  p.deep_hint = h->deep_hint_dev; p.serial = (int)++h->serial;   // the kernels only store the word; the comparison below is unsigned
-  p.pend_hint = h->pend_hint_dev; p.pend_count = h->pend_count;
-  if (h->pend_hint) {
+  const bool flat = !p.hf.fields;
+  if (flat) {
+    p.deep_hint = h->deep_hint_dev; p.serial = (int)++h->serial;   // the kernels only store the word; the comparison below is unsigned
+    p.pend_hint = h->pend_hint_dev; p.pend_count = h->pend_count;
+  }
+  if (flat && h->pend_hint) {
     // estimated hand-overs of the recent launches, one pinned word per launch (ring of 64, read without synchronisation: a stale value
     // changes the schedule, never a result).  The host runs many launches ahead of the device, so the words of the newest launches
     // are still empty: the statistic is the SUM over the last 48 launches (the ones executed by now carry it), compared with what
@@ -198,8 +234,6 @@ void launch_physics_tiers(CassieVec* h, int mode, const cassie::VecParams& pin) 
     h->pend_rate = sum / 16;
     ((volatile unsigned*)h->pend_hint)[h->serial & 63] = 0;   // this launch's word (last used 64 launches ago)
   }
-  cassie::VecParams p2 = p, p3 = p;
-  p3.pending = h->pending; p3.pending_pick = cassie::PICK_ALL;
   // A handed-down environment costs its remaining substeps end to end whatever the batch size (~0.09 ms per substep in the middle
   // tier, 0.13-0.18 ms in the last).  While robots are down the lower tiers therefore take their environments AT THE SAME TIME on
   // two streams: a small kernel tags the environments the middle tier could not hold either (PENDING_DEEP), those go straight to
@@ -211,7 +245,7 @@ void launch_physics_tiers(CassieVec* h, int mode, const cassie::VecParams& pin) 
   // schedule, never a result -- in the one-stream order the middle tier looks at the deep environments first, finds them too
   // large at the same substep, and passes them on untouched).
   // (unsigned difference: wrap-safe; a launch counter that wrapped past a stale hint turns the order on for at most 32 launches)
-  const bool side_by_side = h->leg && (h->side_mode >= 0 ? h->side_mode == 1 : (h->deep_hint && h->serial - (unsigned)*(volatile int*)h->deep_hint <= 32u));
+  const bool side_by_side = flat && h->leg && (h->side_mode >= 0 ? h->side_mode == 1 : (h->deep_hint && h->serial - (unsigned)*(volatile int*)h->deep_hint <= 32u));
   // fork: the side stream waits for the first tier.  If the event cannot be recorded / waited for, fall back to the one-stream order
   // below (same results) rather than let the side stream's kernel run concurrently with the first tier on the same records.
   // in segments only while MANY robots are down: the three extra launches of the first tier cost ~3 % of a step, and a handful of
@@ -248,14 +282,7 @@ void launch_physics_tiers(CassieVec* h, int mode, const cassie::VecParams& pin) 
       const bool fork = !h->seg_failed && hipEventRecord(h->seg_fork[j], h->stream) == hipSuccess &&
                         hipStreamWaitEvent(h->seg_deep[j], h->seg_fork[j], 0) == hipSuccess && hipStreamWaitEvent(h->seg_shal[j], h->seg_fork[j], 0) == hipSuccess;
       if (!fork) h->seg_failed = true;
-      hipStream_t sd = fork ? h->seg_deep[j] : h->stream, ss = fork ? h->seg_shal[j] : h->stream;
-      cassie::VecParams pd = p, pa = p, pb = p;
-      pd.pending = h->seg_pend[j]; pd.pending_pick = cassie::PICK_DEEP;
-      L2::step_k1(mode, L2::K1_DEEP, h->n, sd, pd, L2::K1_HANDOVER_SPLIT);
-      pa.pending = h->seg_pend[j]; pa.pending_pick = cassie::PICK_SHALLOW;
-      L2::step_g16(mode, h->n, ss, pa, h->seg_pend2[j]);
-      pb.pending = h->seg_pend2[j]; pb.pending_pick = cassie::PICK_ALL;
-      L2::step_k1(mode, L2::K1_DEEP, h->n, ss, pb, L2::K1_HANDOVER_SPLIT);
+      launch_lower_tiers(h, mode, p, fork ? h->seg_deep[j] : h->stream, fork ? h->seg_shal[j] : h->stream, h->seg_pend[j], h->seg_pend2[j]);
       forked[j] = fork;
     }
     for (int j = 0; j < nseg; j++) {   // join: the caller's stream continues behind every segment's lower tiers
@@ -269,47 +296,23 @@ void launch_physics_tiers(CassieVec* h, int mode, const cassie::VecParams& pin) 
     return;
   }
   if (side_by_side) {
-    launch_first_tier(h, mode, p, false);
+    launch_first_tier(h, mode, p);
     L2::classify_pending(h->n, h->stream, p, h->pending_leg);
+    // the deep environments on the side stream; no fork: everything on the caller's stream (the deep ones first, then the others)
     const bool forked = hipEventRecord(h->ev_fork, h->stream) == hipSuccess && hipStreamWaitEvent(h->side, h->ev_fork, 0) == hipSuccess;
-    if (forked) {
-      cassie::VecParams pd = p;
-      pd.pending = h->pending_leg; pd.pending_pick = cassie::PICK_DEEP;
-      L2::step_k1(mode, L2::K1_DEEP, h->n, h->side, pd, L2::K1_HANDOVER_SPLIT);
-      const bool joined = hipEventRecord(h->ev_join, h->side) == hipSuccess;
-      p2.pending = h->pending_leg; p2.pending_pick = cassie::PICK_SHALLOW;
-      L2::step_g16(mode, h->n, h->stream, p2, h->pending);
-      L2::step_k1(mode, L2::K1_DEEP, h->n, h->stream, p3, L2::K1_HANDOVER_SPLIT);
-      if (!joined || hipStreamWaitEvent(h->stream, h->ev_join, 0) != hipSuccess) hipStreamSynchronize(h->side);   // join the hard way
-      return;
-    }
-    // no fork: the tagged environments are finished on the caller's stream (the deep ones first, then the others)
-    cassie::VecParams pd = p;
-    pd.pending = h->pending_leg; pd.pending_pick = cassie::PICK_DEEP;
-    L2::step_k1(mode, L2::K1_DEEP, h->n, h->stream, pd, L2::K1_HANDOVER_SPLIT);
-    p2.pending = h->pending_leg; p2.pending_pick = cassie::PICK_SHALLOW;
-    L2::step_g16(mode, h->n, h->stream, p2, h->pending);
-    L2::step_k1(mode, L2::K1_DEEP, h->n, h->stream, p3, L2::K1_HANDOVER_SPLIT);
+    launch_lower_tiers(h, mode, p, forked ? h->side : h->stream, h->stream, h->pending_leg, h->pending);
+    if (forked && (hipEventRecord(h->ev_join, h->side) != hipSuccess || hipStreamWaitEvent(h->stream, h->ev_join, 0) != hipSuccess))
+      hipStreamSynchronize(h->side);   // join the hard way
     return;
   }
+  cassie::VecParams p2 = p, p3 = p;
   if (h->leg) {
-    launch_first_tier(h, mode, p, false);
+    launch_first_tier(h, mode, p);
     p2.pending = h->pending_leg; p2.pending_pick = cassie::PICK_ALL;
   }
   L2::step_g16(mode, h->n, h->stream, p2, h->pending);
-  L2::step_k1(mode, L2::K1_DEEP, h->n, h->stream, p3);
-}
-
-// The same tiers on the height field (one stream: robots on terrain have not been profiled lying down).
-void launch_physics_tiers_hf(CassieVec* h, int mode, const cassie::VecParams& p) {
-  cassie::VecParams p2 = p, p3 = p;
-  if (h->leg) {
-    launch_first_tier(h, mode, p, true);
-    p2.pending = h->pending_leg; p2.pending_pick = cassie::PICK_ALL;
-  }
-  L2::step_g16_hf(mode, h->n, h->stream, p2, h->pending);
   p3.pending = h->pending; p3.pending_pick = cassie::PICK_ALL;
-  L2::step_k1_hf(mode, h->n, h->stream, p3);
+  L2::step_k1(mode, L2::K1_DEEP, h->n, h->stream, p3);
 }
 
 // controller-in-the-loop modes; zpos/zvel != null selects the scripted standing controllers
@@ -330,11 +333,7 @@ int launch_ctrl_step(CassieVec* h, int mode, const cassie::VecParams& p, const d
       ps.n_sub = 1;
       if (sub != p.n_sub - 1) { ps.obs = nullptr; ps.terminal_obs = nullptr; }
       L2::ctrl_g16(ctrl, scripted, h->n, h->stream, ps, zpos, zvel);
-      if (h->hf_n) {
-        launch_physics_tiers_hf(h, 2, ps);
-      } else {
-        launch_physics_tiers(h, 2, ps);
-      }
+      launch_physics_tiers(h, 2, ps);
     }
   } else {
     // wave-per-environment kernels only (CASSIE_WAVE_PER_ENV cross-check, debug record): same split, one wavefront per environment
@@ -344,8 +343,7 @@ int launch_ctrl_step(CassieVec* h, int mode, const cassie::VecParams& p, const d
       if (sub != p.n_sub - 1) { ps.obs = nullptr; ps.terminal_obs = nullptr; }
       L2::ctrl_k4(ctrl, scripted, h->n, h->stream, ps, zpos, zvel);
       ps.debug = nullptr;
-      if (h->hf_n) L2::step_k1_hf(2, h->n, h->stream, ps);
-      else L2::step_k1(2, L2::K1_DEEP, h->n, h->stream, ps);
+      L2::step_k1(2, L2::K1_DEEP, h->n, h->stream, ps);
     }
   }
   HIPCHK(h, hipGetLastError());
@@ -354,16 +352,8 @@ int launch_ctrl_step(CassieVec* h, int mode, const cassie::VecParams& p, const d
 
 int launch_step(CassieVec* h, int mode, const cassie::VecParams& p) {
   const bool pdtq = mode == CASSIE_CTRL_PD || mode == CASSIE_CTRL_TORQUE;
-  if (h->hf_n) {
-    // height-field terrain: the 4-environments-per-wavefront and wave-per-environment kernels with the terrain collision stage
-    if (!pdtq) return launch_ctrl_step(h, mode, p, nullptr, nullptr);
-    if (p.debug) return fail(h, CASSIE_EINVAL, "the debug substep has no height-field variant");
-    if (h->g16) {
-      launch_physics_tiers_hf(h, mode, p);
-    } else {
-      L2::step_k1_hf(mode, h->n, h->stream, p);
-    }
-  } else if (h->g16 && !p.debug && pdtq) {
+  if (p.hf.fields && pdtq && p.debug) return fail(h, CASSIE_EINVAL, "the debug substep has no height-field variant");
+  if (h->g16 && !p.debug && pdtq) {
     // fast path: 4 environments per wavefront; environments with more than 16 active constraint rows are finished
     // by the wave-per-environment kernel, which returns immediately for every other environment
     launch_physics_tiers(h, mode, p);
@@ -390,9 +380,8 @@ int launch_reset(CassieVec* h, const uint8_t* mask, const double* q, const doubl
     L2::get_state(h->n, h->stream, h->state, h->d_q, h->d_v);
     q = h->d_q; v = h->d_v;
   }
-  if (h->hf_n) L2::reset_hf(h->n, h->stream, p, mask, q, v);
-  else if (h->g16 && h->reset_packed && h->need_slow) {
-    // two lanes per environment, 32 environments per wavefront; a state with more than 8 rows on a leg is left to the
+  if (h->g16 && h->reset_packed && h->need_slow && !p.hf.fields) {
+    // two lanes per environment, 32 environments per wavefront (flat floor only); a state with more than 8 rows on a leg is left to the
     // wave-per-environment kernel through the mask the packed kernel writes
     L2::reset_leg(h->n, h->stream, p, mask, q, v, h->need_slow);
     L2::reset(h->n, h->stream, p, h->need_slow, q, v);

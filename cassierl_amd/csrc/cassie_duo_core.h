@@ -43,9 +43,6 @@
 #ifndef CASSIE_DUO_VIEW_FLAG
 #define CASSIE_DUO_VIEW_FLAG 0x20000000   // (DUO_VIEW_EXPERIMENT builds only; no caller sets it)
 #endif
-#ifndef DUO_JOINT8
-#define DUO_JOINT8 1   // groups that leave the six-row path take the eight-row JOINT sweep (r06); 0: the pair sweep inline, as in r05
-#endif
 #ifndef LEG_NOUNROLL
 #define LEG_NOUNROLL _Pragma("clang loop unroll(disable)")
 #endif
@@ -688,24 +685,23 @@ template <class B> struct Duo : Core<B> {
       o[G].do_reset = none; o[G].bad = none;
     });
     B::fence();
-    lds.mark(16);   // (16..21: pieces of the glue, bucket 0 unless the build splits it) 16 = records in, state parked
+    lds.mark(16);   // (16..21: pieces of the glue, bucket 0) 16 = records in, state parked
     bool reset_pass = false;
     int sub = 0;
     while (true) {
       bool join[2] = {false, false}, ran[2] = {false, false};
-      bool join8[2] = {false, false};   // the group's rows are in the workspace in the eight-row format (r06: DUO_JOINT8)
+      bool join8[2] = {false, false};   // the group's rows are in the workspace in the eight-row format (r06: the eight-row joint sweep)
       M ovf[2] = {none, none};
       I nit[2] = {I(0), I(0)};
       lds.snapshot(reset_pass || sub == cfg.n_sub - 1);
       const M lv0 = reset_pass ? o[0].do_reset : live[0], lv1 = reset_pass ? o[1].do_reset : live[1];
-      // ---- phase 1, per group: set-up; a group on its feet hands rows / factorisation to the workspace; a group that needs the eight-row
-      // sweep is carried through at once (pair layout), finish included
+      // ---- phase 1, per group: set-up; a group on its feet hands rows / factorisation to the workspace in the six-row format, a group that
+      // needs more rows in the eight-row format
       LEG_NOUNROLL
       for (int g = 0; g < 2; g++) {
         const M lv = g == 0 ? lv0 : lv1;
         bool ran_ = false, join_ = false, join8_ = false;
         M ovf_ = none;
-        I nit_ = 0;
         if (B::any(lv)) {
           ran_ = true;
           const Io io = io_of(g);
@@ -726,38 +722,24 @@ template <class B> struct Duo : Core<B> {
             lds.mark(10);   // 10 = rows / factorisation out
           };
           auto rows_general = [&]() {
-#if DUO_JOINT8
             // some environment of the group has a joint limit active or a third pair: all eight row slots go to the workspace, with what the finish
             // needs of the once-per-wavefront descriptors, for the eight-row joint sweep
             B::fence();
             put_rows8(ws, base, S); put_keep(ws, base, S); put_misc(ws, base, S.go, S.ncon);
             B::wst(ws, base + W_MISC + 3, B::toD(S.nlim));
             put_desc<HF>(lds, ws, base);
-#endif
           };
           C::template sub_setup<MODE, HF>(lds, st, reset_pass || MODE == 2, lv, !reset_pass, so, S, hf, rows_small, rows_general);
           ovf_ = so.overflow;
           B::fence();
-          if (S.small) {
-            join_ = true;
-          } else {
-#if DUO_JOINT8
-            join8_ = true;
-#else
-            C::sub_sweeps(S);
-            B::fence();
-            nit_ = S.niter;
-            C::template sub_finish<HF>(lds, st, !reset_pass, S);
-            put_lane(ws, base, st);
-#endif
-          }
+          if (S.small) join_ = true;
+          else join8_ = true;
           B::fence();
         }
-        if (g == 0) { ran[0] = ran_; join[0] = join_; join8[0] = join8_; ovf[0] = ovf_; nit[0] = nit_; }
-        else { ran[1] = ran_; join[1] = join_; join8[1] = join8_; ovf[1] = ovf_; nit[1] = nit_; }
+        if (g == 0) { ran[0] = ran_; join[0] = join_; join8[0] = join8_; ovf[0] = ovf_; }
+        else { ran[1] = ran_; join[1] = join_; join8[1] = join8_; ovf[1] = ovf_; }
       }
       // ---- phase 2: one joint sweep for the groups on their feet; the forces go back into the rows' force slots
-#if DUO_JOINT8
       const bool eight = join8[0] || join8[1];
       if (eight) {
         // the eight-row joint sweep: every group of the wavefront in the eight-row format (a group on its feet is widened, a group that does not
@@ -777,9 +759,6 @@ template <class B> struct Duo : Core<B> {
         lds.mark(7);
       }
       if (!eight && (join[0] || join[1])) {
-#else
-      if (join[0] || join[1]) {
-#endif
         Sub S[2];
         lds.mark(0);
         lfor<0, 2>([&](auto gg) {
@@ -824,7 +803,6 @@ template <class B> struct Duo : Core<B> {
           get_misc(ws, base, S1.go, S1.ncon);
           const I nit_ = B::toint(B::wld(ws, base + W_MISC + 2));
           S1.nlim = 0;
-#if DUO_JOINT8
           if (j8) {
             // a group of the eight-row sweep: all eight forces, its joint limits, and the once-per-wavefront descriptors back in LDS
             D t[CAP];
@@ -832,9 +810,7 @@ template <class B> struct Duo : Core<B> {
             lfor<0, CAP>([&](auto ii) { constexpr int Ii = decltype(ii)::value; S1.f[Ii] = t[Ii]; });
             S1.nlim = B::toint(B::wld(ws, base + W_MISC + 3));
             get_desc<HF>(lds, ws, base);
-          } else
-#endif
-          {
+          } else {
           get_forces(ws, base, S1);
           lfor<NR, CAP>([&](auto ii) { constexpr int Ii = decltype(ii)::value; S1.f[Ii] = 0.0; });   // slots 6, 7 are empty in a group on its feet
           }

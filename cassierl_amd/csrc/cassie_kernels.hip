@@ -29,6 +29,7 @@
 #include "cassie2d_planar.h"
 #include "cassie_vec_layout.h"
 #include "cassie_terrain.h"
+#include "cassie_launch.h"
 
 namespace cassie {
 
@@ -1005,6 +1006,23 @@ __global__ void __launch_bounds__(64) env_reset_kernel(VecParams p, const uint8_
   }
   store_state(st, sm, lane, qstate_l, 0.0, so.niter);
 }
+
+namespace launch {
+template <bool HF> void step_k1_tier(int mode, K1Variant variant, int n_envs, hipStream_t s, const VecParams& p, int split) {
+  dim3 grid(p.pending ? (n_envs + 63) / 64 : n_envs, p.pending ? split : 1), block(64);  // hand-over pass: one workgroup scans 64 pending counts
+  if constexpr (!HF) {
+    if (variant == K1_DEBUG) {
+      if (mode == 0) hipLaunchKernelGGL((env_step_kernel<0, 2, K1_MAXACT_DBG>), grid, block, 0, s, p);
+      else hipLaunchKernelGGL((env_step_kernel<1, 2, K1_MAXACT_DBG>), grid, block, 0, s, p);
+      return;
+    }
+  }
+  by_mode(mode, [&](auto m) { hipLaunchKernelGGL((env_step_kernel<m, 1, K1_MAXACT, HF>), grid, block, 0, s, p); });
+}
+template <bool HF> void reset_tier(int n_envs, hipStream_t s, const VecParams& p, const uint8_t* mask, const double* qpos, const double* qvel) {
+  hipLaunchKernelGGL(env_reset_kernel<HF>, dim3(n_envs), dim3(64), 0, s, p, mask, qpos, qvel);
+}
+}  // namespace launch
 
 // The non-template kernels below are compiled by one translation unit only (tu_base.hip).
 #ifdef CASSIE_TU_BASE

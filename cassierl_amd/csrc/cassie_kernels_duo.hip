@@ -17,26 +17,8 @@
 namespace cassie {
 namespace leg {
 
-#ifndef DUO_WAVES
-#define DUO_WAVES 2   // independent wavefronts per workgroup (no barrier, no shared data).  A/B r05, 65 536 envs: 1 -> 1.146 ms, 2 -> 1.125, 4 -> 1.129
-#endif
-#ifndef DUO_STAGGER
-#define DUO_STAGGER 0
-#endif
-#ifndef DUO_WS_PAD
-#define DUO_WS_PAD 0     // slots of padding between the workspaces of two wavefronts (A/B: an odd number of 512-byte slots per wavefront)
-#endif
-#ifndef DUO_WS_LD_AUX
-#define DUO_WS_LD_AUX 0  // cache-policy bits of the workspace loads / stores (A/B: 2 = nt)
-#endif
-#ifndef DUO_WS_ST_AUX
-#define DUO_WS_ST_AUX 0
-#endif
-#if DUO_WAVES == 1
-#define DUO_LANE ((int)threadIdx.x)
-#else
+constexpr int DUO_WAVES = 2;   // independent wavefronts per workgroup (no barrier, no shared data).  A/B r05, 65 536 envs: 1 -> 1.146 ms, 2 -> 1.125, 4 -> 1.129
 #define DUO_LANE ((int)threadIdx.x & 63)
-#endif
 __device__ const double duo_zero_action[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // the action row of a step without actions
 struct DuoShared {
   double cold[2][20][64];    // per group: clock, a2, tau_b 3, tau_l 5, link origins x 5, z 5 (the pelvis origin is the constant 0)
@@ -50,14 +32,11 @@ struct DuoShared {
 static_assert(sizeof(DuoShared) == 39168, "LDS budget of four wavefronts per CU");
 
 struct DevDuoB : DevB {
-#ifndef DUO_SPLIT_TAIL
-#define DUO_SPLIT_TAIL 1
-#endif
   // sub_setup: a group on its feet does not build its two empty row slots and warm-starts over six.  r05 had this off for this kernel (the branch cost 75 more
   // spills with the eight-row pair solve inline behind the set-up: 1.01 -> 1.08 ms); r06: the eight-row groups leave for the joint sweep like the others, the
   // set-up's two branches end in their own stores to the workspace and never meet again: 304 B of scratch instead of 264, **1.018 -> 0.990 ms** per 65 536-env
   // step (tools/ab_bench.py, both orders), bit-identical.
-  static constexpr bool SPLIT_TAIL = DUO_SPLIT_TAIL != 0;
+  static constexpr bool SPLIT_TAIL = true;
   // per-wavefront workspace in global memory (Duo::W_*): [slot][lane], the lane's pointer is the base of its column
   // Buffer addressing: one resource descriptor per wavefront (SGPRs), the lane's byte offset in ONE VGPR, the slot as the scalar offset
   // of the instruction -- so a slot costs an s_mov, not a 64-bit per-lane pointer (with plain pointers the compiler materialises one
@@ -68,20 +47,20 @@ struct DevDuoB : DevB {
   // slots 2p and 2p + 1 of a lane are adjacent: [p][lane][2] -- a pair of slots is ONE sixteen-byte access per lane (1 KB per wavefront)
   static LEG_FN constexpr int wofs(int slot) { return (slot >> 1) * 1024 + (slot & 1) * 8; }
   static LEG_FN double wld(W ws, int slot) {
-    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ws.r, ws.voff, wofs(slot), DUO_WS_LD_AUX);
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ws.r, ws.voff, wofs(slot), 0);
     return __hiloint2double((int)v.y, (int)v.x);
   }
   static LEG_FN void wst(W ws, int slot, double v) {
     u32x2 w; w.x = (unsigned)__double2loint(v); w.y = (unsigned)__double2hiint(v);
-    __builtin_amdgcn_raw_buffer_store_b64(w, ws.r, ws.voff, wofs(slot), DUO_WS_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(w, ws.r, ws.voff, wofs(slot), 0);
   }
   static LEG_FN void wld2(W ws, int slot, double& a, double& b) {   // slot even
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ws.r, ws.voff, wofs(slot), DUO_WS_LD_AUX);
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ws.r, ws.voff, wofs(slot), 0);
     a = __hiloint2double((int)v.y, (int)v.x); b = __hiloint2double((int)v.w, (int)v.z);
   }
   static LEG_FN void wst2(W ws, int slot, double a, double b) {
     u32x4 w; w.x = (unsigned)__double2loint(a); w.y = (unsigned)__double2hiint(a); w.z = (unsigned)__double2loint(b); w.w = (unsigned)__double2hiint(b);
-    __builtin_amdgcn_raw_buffer_store_b128(w, ws.r, ws.voff, wofs(slot), DUO_WS_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(w, ws.r, ws.voff, wofs(slot), 0);
   }
 #ifdef DUO_VIEW_EXPERIMENT
   // the view of joint lane 2e + k on column 2e + X of group k's block (group stride in slots; see joint_solve_view)
@@ -109,11 +88,7 @@ struct DevDuoB : DevB {
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       const unsigned long long n = __builtin_readcyclecounter();
-#ifdef DUO_GLUE_SPLIT   // experiment: the glue in pieces (marks 16..21 -> buckets 1..6), everything else in bucket 7
-      acc[k >= 16 ? k - 15 : k == 0 ? 0 : 7] += n - t_last; t_last = n;
-#else
       acc[k < 16 ? k : 0] += n - t_last; t_last = n;
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
 #else
@@ -175,9 +150,7 @@ typedef Duo<DevDuoB> DDuo;
 static_assert(DDuo::C::C_TIME == 24 && DDuo::C::C_A2 == 28 && DDuo::C::C_TAUB == 29 && DDuo::C::C_OX == 37 && DDuo::C::C_OZ == 43 && DDuo::C::C_N == 49 &&
               DDuo::C::C_KQ == 0 && DDuo::C::C_KV == 8 && DDuo::C::C_QST == 16 && DDuo::C::C_CTRL == 21 && DDuo::C::C_ACT == 25, "DuoLds routes these slot numbers");
 
-// MODE: 0 PD, 1 torque, 2 motor commands from the state record.  pending[env] as env_step_leg_kernel.  workspace: W_N slots x 64 lanes per
-// wavefront SLOT (launch::duo_workspace_bytes; contents only live inside one task of one launch).
-constexpr size_t duo_workspace_doubles_per_wave = (size_t)(DDuo::W_N + DUO_WS_PAD) * 64;
+constexpr size_t duo_workspace_doubles_per_wave = (size_t)DDuo::W_N * 64;
 // THE WORKSPACE IS A PROPERTY OF THE CHIP, NOT OF THE BATCH (r06).  One wavefront of this kernel owns a SIMD (512 registers), so at most
 // 4 x CUs wavefronts exist at any time, however many the launch has.  A batch of up to DuoSlots::DIRECT_MAX tasks (one round of an MI355X,
 // the headline's 65 536 envs) indexes the workspace by its task number, as r05 did.  A larger batch CLAIMS a slot per wavefront from a table
@@ -230,22 +203,24 @@ struct DuoSlots {
   }
 };
 
+inline DuoSlots duo_slots_of(double* workspace, int table_slots, bool flat_hint) {   // host: the launch's claim table (none up to DIRECT_MAX tasks)
+  DuoSlots sl;
+  sl.busy = table_slots ? reinterpret_cast<unsigned*>(workspace + (size_t)table_slots * duo_workspace_doubles_per_wave) : nullptr;
+  sl.mask = table_slots ? (unsigned)table_slots - 1u : 0u;
+  sl.flat_hint = flat_hint ? 1u : 0u;
+  return sl;
+}
+
+// MODE: 0 PD, 1 torque, 2 motor commands from the state record.  pending[env] as env_step_leg_kernel.  workspace: W_N slots x 64 lanes per
+// wavefront SLOT (launch::duo_workspace_bytes; contents only live inside one task of one launch).
 template <int MODE>
 __global__ void __launch_bounds__(64 * DUO_WAVES, 1) env_step_duo_kernel(VecParams p, int* pending, double* workspace, DuoSlots sl) {
-#if DUO_WAVES == 1
-  __shared__ DuoShared sh;
-  const int lane = threadIdx.x;
-  const int wave_id = blockIdx.x;
-#else
   __shared__ DuoShared shs[DUO_WAVES];
   const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);   // wave-uniform: LDS addressing stays on a scalar base
   DuoShared& sh = shs[wv];
   const int lane = threadIdx.x & 63;
   const int wave_id = blockIdx.x * DUO_WAVES + wv;
-#endif
-  EnvCfg cfg;
-  cfg.n_sub = p.n_sub; cfg.flags = p.flags; cfg.env_kind = p.env_kind; cfg.auto_reset = p.auto_reset; cfg.adim = p.adim;
-  cfg.want_obs = p.obs != nullptr; cfg.traj_qpos = p.traj_qpos; cfg.traj_tmax = p.traj_tmax; cfg.traj_n = p.traj_n;
+  const EnvCfg cfg = env_cfg(p);
   bool valid[2];
   size_t e[2];
 #pragma unroll
@@ -257,34 +232,11 @@ __global__ void __launch_bounds__(64 * DUO_WAVES, 1) env_step_duo_kernel(VecPara
   // the group's per-lane pointers, rebuilt where a phase needs them (held for the whole kernel they are 24 registers the allocator spills)
   auto io_of = [&](int g) {
     const int env = wave_id * 64 + g * 32 + (lane >> 1);
-    const size_t eg = env < p.n_envs ? (size_t)env : 0;
-    DDuo::Io io;
-    io.rec = p.state + eg * ENV_STRIDE;
-    io.has_act = p.actions != nullptr;
-    io.act = const_cast<double*>(p.actions) + (io.has_act ? eg * p.adim : 0);
-    io.obs = p.obs + (cfg.want_obs ? eg * 26 : 0);
-    io.has_tobs = p.terminal_obs != nullptr;
-    io.tobs = p.terminal_obs + (io.has_tobs ? eg * 26 : 0);
-    io.rew = p.reward + (cfg.want_obs ? eg : 0);
-    io.done = p.done + (cfg.want_obs ? eg : 0);
-    return io;
+    return env_io<DDuo::Io>(p, env < p.n_envs ? (size_t)env : 0, cfg.want_obs);
   };
   DevDuoB::Lds lds;
   lds.sh = &sh; lds.g = 0; lds.rec = p.state; lds.act = p.actions; lds.has_act = false; lds.snap = true;
   lds.lo = (lane & 1) * 5 + 3; lds.ao = (lane & 1) * 3;
-#if DUO_STAGGER > 0
-  // Stagger: every wavefront runs the same phases for the same time, so all 128 wavefronts of an XCD hit its L2 with their hand-over bursts at
-  // once (phase clocks, r05: 16 % of a wavefront's time in the hand-over, at ~60 cycles per 512-byte access = the L2's bandwidth shared by 128).
-  // Eight start classes DUO_STAGGER x 3.4 us apart keep the bursts of most wavefronts apart for the whole launch.
-  {
-#if DUO_WAVES == 1
-    const int cls = (blockIdx.x >> 3) & 7;
-#else
-    const int cls = (((blockIdx.x >> 3) & 3) * 2 + (wv & 1)) & 7;
-#endif
-    for (int i = 0; i < cls * DUO_STAGGER; i++) __builtin_amdgcn_s_sleep(127);
-  }
-#endif
   DDuo::Out o[2];
   DevDuoB::W ws;   // raw buffer over this wavefront's W_N x 512 bytes (word 3: 32-bit data format, gfx9 encoding)
   const int slot = sl.claim(lane, wave_id, p.stats);
@@ -301,17 +253,9 @@ __global__ void __launch_bounds__(64 * DUO_WAVES, 1) env_step_duo_kernel(VecPara
   if (lane == 0 && p.phase) for (int i = 0; i < 16; i++) atomicAdd(p.phase + i, lds.acc[i]);
 #endif
 #pragma unroll
-  for (int g = 0; g < 2; g++) {
-    if (valid[g] && (lane & 1) == 0) {
-      pending[e[g]] = o[g].pend;
-      if (p.stats) {
-        if (o[g].pend > 0) atomicAdd(p.stats + STAT_CLEANUP_SUBSTEPS, (unsigned long long)o[g].pend);
-        if (o[g].bad) atomicAdd(p.stats + STAT_NONFINITE, 1ull);
-      }
-    }
-  }
+  for (int g = 0; g < 2; g++)
+    if (valid[g] && (lane & 1) == 0) report(p, pending, e[g], o[g].pend, o[g].bad);
 }
-
 
 #ifdef CASSIE_LEG_HF
 // ---------------------------------------------------------------- height-field instantiation (tu_duo_hf.hip)
@@ -355,20 +299,12 @@ static_assert(DDuoHF::W_N == DDuo::W_N, "one workspace size for both instantiati
 
 template <int MODE>
 __global__ void __launch_bounds__(64 * DUO_WAVES, 1) env_step_duo_hf_kernel(VecParams p, int* pending, double* workspace, DuoSlots sl) {
-#if DUO_WAVES == 1
-  __shared__ DuoSharedHF sh;
-  const int lane = threadIdx.x;
-  const int wave_id = blockIdx.x;
-#else
   __shared__ DuoSharedHF shs[DUO_WAVES];
   const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   DuoSharedHF& sh = shs[wv];
   const int lane = threadIdx.x & 63;
   const int wave_id = blockIdx.x * DUO_WAVES + wv;
-#endif
-  EnvCfg cfg;
-  cfg.n_sub = p.n_sub; cfg.flags = p.flags; cfg.env_kind = p.env_kind; cfg.auto_reset = p.auto_reset; cfg.adim = p.adim;
-  cfg.want_obs = p.obs != nullptr; cfg.traj_qpos = p.traj_qpos; cfg.traj_tmax = p.traj_tmax; cfg.traj_n = p.traj_n;
+  const EnvCfg cfg = env_cfg(p);
   bool valid[2];
   size_t e[2];
 #pragma unroll
@@ -379,17 +315,7 @@ __global__ void __launch_bounds__(64 * DUO_WAVES, 1) env_step_duo_hf_kernel(VecP
   }
   auto io_of = [&](int g) {
     const int env = wave_id * 64 + g * 32 + (lane >> 1);
-    const size_t eg = env < p.n_envs ? (size_t)env : 0;
-    DDuoHF::Io io;
-    io.rec = p.state + eg * ENV_STRIDE;
-    io.has_act = p.actions != nullptr;
-    io.act = const_cast<double*>(p.actions) + (io.has_act ? eg * p.adim : 0);
-    io.obs = p.obs + (cfg.want_obs ? eg * 26 : 0);
-    io.has_tobs = p.terminal_obs != nullptr;
-    io.tobs = p.terminal_obs + (io.has_tobs ? eg * 26 : 0);
-    io.rew = p.reward + (cfg.want_obs ? eg : 0);
-    io.done = p.done + (cfg.want_obs ? eg : 0);
-    return io;
+    return env_io<DDuoHF::Io>(p, env < p.n_envs ? (size_t)env : 0, cfg.want_obs);
   };
   DevDuoBHF::Lds lds;
   lds.sh = &sh; lds.shf = &sh; lds.g = 0; lds.rec = p.state; lds.act = p.actions; lds.has_act = false; lds.snap = true;
@@ -407,18 +333,25 @@ __global__ void __launch_bounds__(64 * DUO_WAVES, 1) env_step_duo_hf_kernel(VecP
   DDuoHF::env_step2<MODE, true>(cfg, lds, ws, io_of, valid, o, p.hf.fields);
   sl.release(lane, slot);
 #pragma unroll
-  for (int g = 0; g < 2; g++) {
-    if (valid[g] && (lane & 1) == 0) {
-      pending[e[g]] = o[g].pend;
-      if (p.stats) {
-        if (o[g].pend > 0) atomicAdd(p.stats + STAT_CLEANUP_SUBSTEPS, (unsigned long long)o[g].pend);
-        if (o[g].bad) atomicAdd(p.stats + STAT_NONFINITE, 1ull);
-      }
-    }
-  }
+  for (int g = 0; g < 2; g++)
+    if (valid[g] && (lane & 1) == 0) report(p, pending, e[g], o[g].pend, o[g].bad);
 }
+#else
+template <int MODE> __global__ void env_step_duo_hf_kernel(VecParams p, int* pending, double* workspace, DuoSlots sl);   // (declared for step_duo_tier<true>: tu_duo_hf.hip)
 #endif
 
 }  // namespace leg
+
+namespace launch {
+template <bool HF> void step_duo_tier(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending, double* workspace, int table_slots, bool flat_hint) {
+  const leg::DuoSlots sl = leg::duo_slots_of(workspace, table_slots, flat_hint);
+  const int waves = (n_envs + 63) / 64;
+  dim3 grid((waves + leg::DUO_WAVES - 1) / leg::DUO_WAVES), block(64 * leg::DUO_WAVES);
+  by_mode(mode, [&](auto m) {
+    if constexpr (HF) hipLaunchKernelGGL((leg::env_step_duo_hf_kernel<m>), grid, block, 0, s, p, pending, workspace, sl);
+    else hipLaunchKernelGGL((leg::env_step_duo_kernel<m>), grid, block, 0, s, p, pending, workspace, sl);
+  });
+}
+}  // namespace launch
 }  // namespace cassie
 #endif

@@ -790,5 +790,11 @@ __global__ void __launch_bounds__(64, 2) classify_pending_kernel(VecParams p, in
 #endif
 
 }  // namespace g16
+
+namespace launch {
+template <bool HF> void step_g16_tier(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending) {
+  by_mode(mode, [&](auto m) { hipLaunchKernelGGL((g16::env_step_g16_kernel<m, HF>), dim3((n_envs + 3) / 4), dim3(64), 0, s, p, pending); });
+}
+}  // namespace launch
 }  // namespace cassie
 #endif

@@ -18,6 +18,7 @@
 
 #define LEG_FN __device__ __forceinline__
 #include "cassie_leg_core.h"
+#include "cassie_launch.h"
 
 namespace cassie {
 namespace leg {
@@ -76,11 +77,7 @@ struct DevB {
     }
   };
   static LEG_FN int leg() { return (int)threadIdx.x & 1; }
-#ifdef LEG_NO_FENCE
-  static LEG_FN void fence() {}
-#else
-  static LEG_FN void fence() { __builtin_amdgcn_sched_barrier(0); }
-#endif   // nothing is scheduled across this point
+  static LEG_FN void fence() { __builtin_amdgcn_sched_barrier(0); }   // nothing is scheduled across this point
   static LEG_FN int opq(int x) { asm volatile("" : "+v"(x)); return x; }     // the value, unknown to the optimiser
   static LEG_FN int zs() { int z = 0; asm volatile("" : "+s"(z)); return z; }  // a wave-uniform zero, unknown to the optimiser
   static LEG_FN double sel(bool m, double a, double b) { return m ? a : b; }
@@ -123,6 +120,34 @@ struct DevB {
 
 typedef Core<DevB> DCore;
 
+// The entry of every kernel of this file and of cassie_kernels_duo.hip: the step's settings, the environment's rows of the batch arrays (e: an
+// environment that exists), the tier's outputs for one environment (its even lane).
+LEG_FN EnvCfg env_cfg(const VecParams& p) {
+  EnvCfg cfg;
+  cfg.n_sub = p.n_sub; cfg.flags = p.flags; cfg.env_kind = p.env_kind; cfg.auto_reset = p.auto_reset; cfg.adim = p.adim;
+  cfg.want_obs = p.obs != nullptr; cfg.traj_qpos = p.traj_qpos; cfg.traj_tmax = p.traj_tmax; cfg.traj_n = p.traj_n;
+  return cfg;
+}
+template <class Io> LEG_FN Io env_io(const VecParams& p, size_t e, bool want_obs) {
+  Io io;
+  io.rec = p.state + e * ENV_STRIDE;
+  io.has_act = p.actions != nullptr;
+  io.act = const_cast<double*>(p.actions) + (io.has_act ? e * p.adim : 0);
+  io.obs = p.obs + (want_obs ? e * 26 : 0);
+  io.has_tobs = p.terminal_obs != nullptr;
+  io.tobs = p.terminal_obs + (io.has_tobs ? e * 26 : 0);
+  io.rew = p.reward + (want_obs ? e : 0);
+  io.done = p.done + (want_obs ? e : 0);
+  return io;
+}
+LEG_FN void report(const VecParams& p, int* pending, size_t e, int pend, bool bad) {
+  pending[e] = pend;
+  if (p.stats) {
+    if (pend > 0) atomicAdd(p.stats + STAT_CLEANUP_SUBSTEPS, (unsigned long long)pend);
+    if (bad) atomicAdd(p.stats + STAT_NONFINITE, 1ull);
+  }
+}
+
 // MODE: 0 PD, 1 torque, 2 motor commands from the state record.  pending[env] = substeps this kernel did NOT do because the
 // environment needed more than 8 constraint rows on a leg (0 normally); the packed 16-row kernel / the wave-per-environment
 // kernel finish those (cassie_cabi.hip).
@@ -133,18 +158,8 @@ __global__ void __launch_bounds__(64, 1) env_step_leg_kernel(VecParams p, int* p
   const int env = blockIdx.x * 32 + (lane >> 1);
   const bool valid = env < p.n_envs;
   const size_t e = valid ? (size_t)env : 0;
-  EnvCfg cfg;
-  cfg.n_sub = p.n_sub; cfg.flags = p.flags; cfg.env_kind = p.env_kind; cfg.auto_reset = p.auto_reset; cfg.adim = p.adim;
-  cfg.want_obs = p.obs != nullptr; cfg.traj_qpos = p.traj_qpos; cfg.traj_tmax = p.traj_tmax; cfg.traj_n = p.traj_n;
-  DCore::Io io;
-  io.rec = p.state + e * ENV_STRIDE;
-  io.has_act = p.actions != nullptr;
-  io.act = const_cast<double*>(p.actions) + (io.has_act ? e * p.adim : 0);
-  io.obs = p.obs + (cfg.want_obs ? e * 26 : 0);
-  io.has_tobs = p.terminal_obs != nullptr;
-  io.tobs = p.terminal_obs + (io.has_tobs ? e * 26 : 0);
-  io.rew = p.reward + (cfg.want_obs ? e : 0);
-  io.done = p.done + (cfg.want_obs ? e : 0);
+  const EnvCfg cfg = env_cfg(p);
+  DCore::Io io = env_io<DCore::Io>(p, e, cfg.want_obs);
 #ifdef CASSIE_PHASE_TIMING
   if (lane == 0) { for (int i = 0; i < 16; i++) lds.acc[i] = 0; lds.t_last = __builtin_readcyclecounter(); }
 #endif
@@ -154,13 +169,7 @@ __global__ void __launch_bounds__(64, 1) env_step_leg_kernel(VecParams p, int* p
   lds.mark(0);
   if (lane == 0 && p.phase) for (int i = 0; i < 16; i++) atomicAdd(p.phase + i, lds.acc[i]);
 #endif
-  if (valid && (lane & 1) == 0) {
-    pending[e] = o.pend;
-    if (p.stats) {
-      if (o.pend > 0) atomicAdd(p.stats + STAT_CLEANUP_SUBSTEPS, (unsigned long long)o.pend);
-      if (o.bad) atomicAdd(p.stats + STAT_NONFINITE, 1ull);
-    }
-  }
+  if (valid && (lane & 1) == 0) report(p, pending, e, o.pend, o.bad);
 }
 
 #ifdef CASSIE_LEG_SEGMENT   // tu_leg_seg.hip only: a separate translation unit, so that the kernel above compiles to what it was
@@ -179,9 +188,7 @@ __global__ void __launch_bounds__(64, 1) env_step_leg_seg_kernel(VecParams p, in
   const bool exists = env < p.n_envs;
   const bool valid = exists && (seg.first || gone[env] == 0);
   const size_t e = valid ? (size_t)env : 0;
-  EnvCfg cfg;
-  cfg.n_sub = p.n_sub; cfg.flags = p.flags; cfg.env_kind = p.env_kind; cfg.auto_reset = p.auto_reset; cfg.adim = p.adim;
-  cfg.want_obs = p.obs != nullptr; cfg.traj_qpos = p.traj_qpos; cfg.traj_tmax = p.traj_tmax; cfg.traj_n = p.traj_n;
+  EnvCfg cfg = env_cfg(p);
   cfg.pend_extra = seg.later; cfg.cont = !seg.first;
   DCore::Io io;
   io.rec = p.state + e * ENV_STRIDE;
@@ -215,13 +222,10 @@ __global__ void __launch_bounds__(64, 1) env_reset_leg_kernel(VecParams p, const
   const bool exists = env < p.n_envs;
   const bool want = exists && (!mask || mask[env]);
   const size_t e = exists ? (size_t)env : 0;
-  EnvCfg cfg;
-  cfg.n_sub = 0; cfg.flags = p.flags; cfg.env_kind = p.env_kind; cfg.auto_reset = p.auto_reset; cfg.adim = p.adim;
-  cfg.want_obs = p.obs != nullptr; cfg.traj_qpos = p.traj_qpos; cfg.traj_tmax = p.traj_tmax; cfg.traj_n = p.traj_n;
-  DCore::Io io;
-  io.rec = p.state + e * ENV_STRIDE;
+  EnvCfg cfg = env_cfg(p);
+  cfg.n_sub = 0;
+  DCore::Io io = env_io<DCore::Io>(p, e, cfg.want_obs);
   io.has_act = false; io.act = io.rec;
-  io.obs = p.obs + (cfg.want_obs ? e * 26 : 0);
   io.has_tobs = false; io.tobs = io.obs; io.rew = io.rec; io.done = nullptr;
   const bool has_qv = qpos_in != nullptr;
   DCore::Out o;
@@ -259,31 +263,28 @@ __global__ void __launch_bounds__(64, 1) env_step_leg_hf_kernel(VecParams p, int
   const int env = blockIdx.x * 32 + (lane >> 1);
   const bool valid = env < p.n_envs;
   const size_t e = valid ? (size_t)env : 0;
-  EnvCfg cfg;
-  cfg.n_sub = p.n_sub; cfg.flags = p.flags; cfg.env_kind = p.env_kind; cfg.auto_reset = p.auto_reset; cfg.adim = p.adim;
-  cfg.want_obs = p.obs != nullptr; cfg.traj_qpos = p.traj_qpos; cfg.traj_tmax = p.traj_tmax; cfg.traj_n = p.traj_n;
-  DCoreHF::Io io;
-  io.rec = p.state + e * ENV_STRIDE;
-  io.has_act = p.actions != nullptr;
-  io.act = const_cast<double*>(p.actions) + (io.has_act ? e * p.adim : 0);
-  io.obs = p.obs + (cfg.want_obs ? e * 26 : 0);
-  io.has_tobs = p.terminal_obs != nullptr;
-  io.tobs = p.terminal_obs + (io.has_tobs ? e * 26 : 0);
-  io.rew = p.reward + (cfg.want_obs ? e : 0);
-  io.done = p.done + (cfg.want_obs ? e : 0);
+  const EnvCfg cfg = env_cfg(p);
+  DCoreHF::Io io = env_io<DCoreHF::Io>(p, e, cfg.want_obs);
   lds.fid[lane] = terrain_id(p.hf.ids, p.hf.n_fields, (int)e);
   DCoreHF::Out o;
   DCoreHF::env_step<MODE, true>(cfg, lds, io, valid, o, p.hf.fields);
-  if (valid && (lane & 1) == 0) {
-    pending[e] = o.pend;
-    if (p.stats) {
-      if (o.pend > 0) atomicAdd(p.stats + STAT_CLEANUP_SUBSTEPS, (unsigned long long)o.pend);
-      if (o.bad) atomicAdd(p.stats + STAT_NONFINITE, 1ull);
-    }
-  }
+  if (valid && (lane & 1) == 0) report(p, pending, e, o.pend, o.bad);
 }
+#else
+template <int MODE> __global__ void env_step_leg_hf_kernel(VecParams p, int* pending);   // (declared for step_leg_tier<true>: tu_hf.hip)
 #endif
 
 }  // namespace leg
+
+namespace launch {
+template <bool HF> void step_leg_tier(int mode, int n_envs, hipStream_t s, const VecParams& p, int* pending) {
+  dim3 grid((n_envs + 31) / 32), block(64);
+  by_mode(mode, [&](auto m) {
+    if constexpr (HF) hipLaunchKernelGGL((leg::env_step_leg_hf_kernel<m>), grid, block, 0, s, p, pending);
+    else hipLaunchKernelGGL((leg::env_step_leg_kernel<m>), grid, block, 0, s, p, pending);
+  });
+}
+}  // namespace launch
+
 }  // namespace cassie
 #endif

@@ -6,20 +6,8 @@
 namespace cassie {
 namespace launch {
 
-void step_k1(int mode, K1Variant variant, int n_envs, hipStream_t s, const VecParams& p, int split) {
-  dim3 grid(p.pending ? (n_envs + 63) / 64 : n_envs, p.pending ? split : 1), block(64);  // hand-over pass: one workgroup scans 64 pending counts
-  if (variant == K1_DEBUG) {
-    if (mode == 0) hipLaunchKernelGGL((env_step_kernel<0, 2, K1_MAXACT_DBG>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((env_step_kernel<1, 2, K1_MAXACT_DBG>), grid, block, 0, s, p);
-  } else {
-    if (mode == 0) hipLaunchKernelGGL((env_step_kernel<0, 1, K1_MAXACT>), grid, block, 0, s, p);
-    else if (mode == 1) hipLaunchKernelGGL((env_step_kernel<1, 1, K1_MAXACT>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((env_step_kernel<2, 1, K1_MAXACT>), grid, block, 0, s, p);
-  }
-}
-void reset(int n_envs, hipStream_t s, const VecParams& p, const uint8_t* mask, const double* qpos, const double* qvel) {
-  hipLaunchKernelGGL(env_reset_kernel<false>, dim3(n_envs), dim3(64), 0, s, p, mask, qpos, qvel);
-}
+template void step_k1_tier<false>(int, K1Variant, int, hipStream_t, const VecParams&, int);
+template void reset_tier<false>(int, hipStream_t, const VecParams&, const uint8_t*, const double*, const double*);
 void opstate(int n_envs, hipStream_t s, const VecParams& p, double* out18) {
   hipLaunchKernelGGL(env_opstate_kernel, dim3(n_envs), dim3(64), 0, s, p, out18);
 }
