@@ -30,6 +30,8 @@ EXPORTS = [
     # fused policy kernels of the TRPO outer loop (include/cassie_trpo.h)
     "CassieTrpoParamCount", "CassieTrpoPartialRows", "CassieTrpoFvp", "CassieTrpoVjp", "CassieTrpoSurrogate", "CassieTrpoCgUpdate", "CassieTrpoPolicyStep", "CassieTrpoSamplerRows", "CassieTrpoSamplerStep",
     "CassieTrpoBaselineFeatures", "CassieTrpoBaselinePredict", "CassieTrpoReturnsAdvantages", "CassieTrpoGramRows", "CassieTrpoGramRowSize", "CassieTrpoBaselineGram", "CassieTrpoRidgeSolve",
+    # width-128 policy (include/cassie_trpo.h)
+    "CassiePgParamCount", "CassiePgPolicyStep", "CassiePgPartialRows", "CassiePgVjp", "CassiePgAdam",
 ]
 
 

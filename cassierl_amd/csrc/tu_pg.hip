@@ -1,0 +1,376 @@
+// tu_pg.hip -- fused kernels of the width-128 policy (include/cassie_trpo.h, "width-128 policy"; rllab/envs/vpg_cassie.py:15-48):
+// the sampler's policy step, the policy gradient J' w of the 128-128 tanh mean network, and Lasagne's Adam step.
+//
+// The layout is tu_trpo.hip's (read its header first): exact float32 v_mfma_f32_32x32x2_f32, a tile of 32 samples per wavefront, every
+// activation in the accumulator layout (sample on the lane c = lane & 31, hidden unit r(v, h) = (v & 3) + 8 (v >> 2) + 4 h in register v),
+// so that tanh and 1 - h^2 are register-wise and a layer takes the previous activation's registers as its B operand.  A 128-wide layer
+// is four 32-row blocks (v16f[4], 64 registers); the 128 x 128 layer is 4 x 4 blocks of 16 k-steps (256 MFMAs per tile).
+//
+// Differences from the width-32 kernels, and why:
+//   * the A operands are read straight from global memory (L1 / L2), not from a per-workgroup LDS image.  In the accumulator order the
+//     four k-steps 4 g .. 4 g + 3 of lane (c, h) are W[row][32 kb + 8 g + 4 h + 0..3]: one aligned float4 of a row-major weight.  At
+//     65 536 environments there are two tiles per SIMD, so an image (93 KB per workgroup) would be read from L2 about as often as the
+//     weights themselves, and it would allow one workgroup per CU.  The policy step runs one tile per wavefront: with a tile loop the
+//     compiler hoists a tile's 372 weight loads out of it and spills;
+//   * the VJP's gradient accumulators do not fit one wavefront (gW2 alone is 256 registers per lane).  The four wavefronts of a
+//     workgroup each run the forward and backward pass of their own tile and put its transposed tiles in LDS (two slots of
+//     4 x 128 x 36 floats = 144 KB, three exchanges per group of four tiles: H1 and H2, then G2, then G1), and wavefront q accumulates
+//     the 32-row quarter q of gW1, gW2 and the 32-column quarter q of gW3 from all four tiles (96 accumulator registers).  One row of
+//     partial sums per WORKGROUP; the caller adds the rows;
+//   * the 6- or 7-row output layer is padded to 32 rows, as in tu_trpo.hip (64 of the 372 MFMAs of a forward tile).
+// Every sum runs in a fixed order (k-ordered MFMA chains, tiles in a fixed order per workgroup, a fixed grid for a given n): a run
+// repeats bit for bit.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/cassie_trpo.h"
+#include "../../include/cassie_vec.h"
+
+namespace cassie_pg {
+
+constexpr int H = 128;            // hidden units (both layers)
+constexpr int NB = H / 32;        // 32-row blocks of a hidden layer
+constexpr int TP = 36;            // floats per row of a transposed tile (16-byte aligned rows, ds_read_b128 conflict-free)
+constexpr int WAVES = 4;          // wavefronts per workgroup: one per SIMD
+constexpr int MAX_VJP_BLOCKS = 256;   // one VJP workgroup per CU (144 KB of LDS)
+
+template <int D, int A> struct Shape {
+  static constexpr int NP = H * D + H + H * H + H + A * H + A;
+  static constexpr int O_W1 = 0, O_B1 = H * D, O_W2 = O_B1 + H, O_B2 = O_W2 + H * H, O_W3 = O_B2 + H, O_B3 = O_W3 + A * H;
+};
+
+struct Net { const float *W1, *b1, *W2, *b2, *W3, *b3; };
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+#define PG_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+
+// tanh through the hardware exp2 / rcp, as in tu_trpo.hip: 1 - 2 / (e^2x + 1)
+__device__ __forceinline__ float tanh_fast(float x) {
+  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
+  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
+}
+
+__device__ __forceinline__ v16f zero16() {
+  v16f z;
+#pragma unroll
+  for (int v = 0; v < 16; v++) z[v] = 0.0f;
+  return z;
+}
+
+// C operand: b[r(v, h)] in register v (rows 8 g + 4 h .. + 3 are one float4)
+__device__ __forceinline__ v16f bias_tile(const float* __restrict__ b, int h) {
+  v16f z;
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    const float4 x = *reinterpret_cast<const float4*>(b + 8 * g + 4 * h);
+    z[4 * g] = x.x; z[4 * g + 1] = x.y; z[4 * g + 2] = x.z; z[4 * g + 3] = x.w;
+  }
+  return z;
+}
+
+// y += W[row0 + c][col0 + r(v, h)] x[v] over the 16 k-steps (W row-major with ld floats per row; col0 and ld multiples of 4)
+__device__ __forceinline__ void gemm_block(const float* __restrict__ W, int ld, int row0, int col0, bool on, const v16f& x, v16f& y, int c, int h) {
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (on) a = *reinterpret_cast<const float4*>(W + (size_t)(row0 + c) * ld + col0 + 8 * g + 4 * h);
+    y = PG_MFMA(a.x, x[4 * g], y); y = PG_MFMA(a.y, x[4 * g + 1], y); y = PG_MFMA(a.z, x[4 * g + 2], y); y = PG_MFMA(a.w, x[4 * g + 3], y);
+  }
+}
+
+// Forward pass of one tile: h1 = tanh(W1 x + b1), h2 = tanh(W2 h1 + b2) (four blocks each); first layer k = 2 s + h
+template <int D>
+__device__ __forceinline__ void forward_hidden(const Net& th, const float (&xb)[(D + 1) / 2], v16f (&h1)[NB], v16f (&h2)[NB], int c, int h) {
+  constexpr int KS1 = (D + 1) / 2;
+#pragma unroll
+  for (int ob = 0; ob < NB; ob++) {
+    v16f y = bias_tile(th.b1 + 32 * ob, h);
+#pragma unroll
+    for (int s = 0; s < KS1; s++) {
+      const int k = 2 * s + h;
+      const float a = k < D ? th.W1[(32 * ob + c) * D + k] : 0.0f;
+      y = PG_MFMA(a, xb[s], y);
+    }
+#pragma unroll
+    for (int v = 0; v < 16; v++) y[v] = tanh_fast(y[v]);
+    h1[ob] = y;
+  }
+#pragma unroll
+  for (int ob = 0; ob < NB; ob++) {
+    v16f y = bias_tile(th.b2 + 32 * ob, h);
+#pragma unroll
+    for (int kb = 0; kb < NB; kb++) gemm_block(th.W2, H, 32 * ob, 32 * kb, true, h1[kb], y, c, h);
+#pragma unroll
+    for (int v = 0; v < 16; v++) y[v] = tanh_fast(y[v]);
+    h2[ob] = y;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- policy step
+// CassieTrpoPolicyStep's contract for the 128-128 network: a wavefront per tile of 32 environments; the mean comes out with action
+// a = v + 4 h in register v < 4 of lane (environment, h).
+template <int D, int A>
+__global__ void __launch_bounds__(64 * WAVES, 2) pg_policy_step_kernel(const double* __restrict__ obs, int n, Net th, const float* __restrict__ log_std,
+                                                                   const float* __restrict__ noise, const double* __restrict__ low, const double* __restrict__ high,
+                                                                   float* __restrict__ obs32, float* __restrict__ mean, float* __restrict__ act, double* __restrict__ env_act) {
+  constexpr int KS1 = (D + 1) / 2;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, h = lane >> 5;
+  float sd[4];
+  double lo[4], hi[4];
+#pragma unroll
+  for (int v = 0; v < 4; v++) {
+    const int a = v + 4 * h;
+    sd[v] = a < A ? expf(log_std[a]) : 0.0f;
+    lo[v] = a < A ? low[a] : 0.0; hi[v] = a < A ? high[a] : 0.0;
+  }
+  {   // one tile per wavefront: no loop for the compiler to hoist the 372 weight loads of a tile out of (they would not fit in registers)
+    const int smp = (blockIdx.x * WAVES + wave) * 32 + c;
+    const bool valid = smp < n;
+    float xb[KS1];
+#pragma unroll
+    for (int s = 0; s < KS1; s++) {
+      const int k = 2 * s + h;
+      const bool on = valid && k < D;
+      xb[s] = on ? (float)obs[(size_t)smp * D + k] : 0.0f;
+      if (on) obs32[(size_t)smp * D + k] = xb[s];
+    }
+    v16f h1[NB], h2[NB];
+    forward_hidden<D>(th, xb, h1, h2, c, h);
+    v16f mu;
+#pragma unroll
+    for (int v = 0; v < 16; v++) mu[v] = (v < 4 && v + 4 * h < A) ? th.b3[v + 4 * h] : 0.0f;
+#pragma unroll
+    for (int kb = 0; kb < NB; kb++) gemm_block(th.W3, H, 0, 32 * kb, c < A, h2[kb], mu, c, h);
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+      const int a = v + 4 * h;
+      if (valid && a < A) {
+        const size_t o = (size_t)smp * A + a;
+        const float val = mu[v] + noise[o] * sd[v];
+        mean[o] = mu[v]; act[o] = val;
+        double e = lo[v] + ((double)val + 1.0) * 0.5 * (hi[v] - lo[v]);
+        e = e < lo[v] ? lo[v] : (e > hi[v] ? hi[v] : e);
+        env_act[o] = e;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- VJP
+__device__ __forceinline__ void wave_put(float* __restrict__ t, const v16f (&x)[NB], int c, int h) {   // accumulator layout -> [row][sample]
+#pragma unroll
+  for (int b = 0; b < NB; b++)
+#pragma unroll
+    for (int v = 0; v < 16; v++) t[(32 * b + (v & 3) + 8 * (v >> 2) + 4 * h) * TP + c] = x[b][v];
+}
+__device__ __forceinline__ void wave_get(const float* __restrict__ t, float (&y)[16], int c, int h) {   // lane (c, h): row c, samples 16 h .. 16 h + 15
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const float4 b = *reinterpret_cast<const float4*>(&t[c * TP + 16 * h + 4 * q]);
+    y[4 * q] = b.x; y[4 * q + 1] = b.y; y[4 * q + 2] = b.z; y[4 * q + 3] = b.w;
+  }
+}
+
+// partial [gridDim.x][NP]: J' w of this workgroup's tiles, [gW1 | gb1 | gW2 | gb2 | gW3 | gb3].  Wavefront q writes rows 32 q .. 32 q + 31
+// of gW1 / gb1 / gW2 / gb2 and columns 32 q .. 32 q + 31 of gW3; wavefront 0 writes gb3.
+template <int D, int A>
+__global__ void __launch_bounds__(64 * WAVES, 1) pg_vjp_kernel(const float* __restrict__ obs, int n, Net th0, const float* __restrict__ wext, float* __restrict__ partial) {
+  typedef Shape<D, A> S;
+  static_assert(D < 32 && A <= 8, "a column of ones next to the observations; the cotangent rows in registers 0..3 of the two lane halves");
+  constexpr int KS1 = (D + 1) / 2;
+  __shared__ alignas(16) float stage[2][WAVES][H * TP];
+  __shared__ Net snet;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, h = lane >> 5;
+  if (tid == 0) snet = th0;
+  v16f gW2[NB], gW1 = zero16(), gW3 = zero16();
+#pragma unroll
+  for (int b = 0; b < NB; b++) gW2[b] = zero16();
+  float gb2 = 0.0f, gb3 = 0.0f;
+  const int ntiles = (n + 31) / 32, ngroups = (ntiles + WAVES - 1) / WAVES;
+  for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {   // the same trip count for every wavefront of the workgroup
+    // The weight pointers are re-read from LDS behind the barrier: loads through them cannot be hoisted out of the loop (the compiler
+    // otherwise keeps ~800 weight values of a tile in registers across the iterations, and spills).  The barrier also orders this
+    // group's first LDS writes after the previous group's last reads.
+    __syncthreads();
+    const Net th = snet;
+    const int gs0 = grp * WAVES * 32;                               // first sample of the group; tile u starts at gs0 + 32 u
+    const int s0 = gs0 + 32 * wave, smp = s0 + c;
+    const bool valid = smp < n;                                    // a tile past the end runs with w = 0: its G2, G1 are zero
+    float xb[KS1];
+#pragma unroll
+    for (int s = 0; s < KS1; s++) { const int k = 2 * s + h; xb[s] = (valid && k < D) ? obs[(size_t)smp * D + k] : 0.0f; }
+    v16f h1[NB], h2[NB], g2[NB], g1[NB];
+    forward_hidden<D>(th, xb, h1, h2, c, h);
+    float wt[4];
+#pragma unroll
+    for (int v = 0; v < 4; v++) wt[v] = (valid && v + 4 * h < A) ? wext[(size_t)smp * A + v + 4 * h] : 0.0f;
+    // G2 = (W3' w) o (1 - H2^2): k-step v sums over the cotangent row a = v + 4 h
+#pragma unroll
+    for (int ob = 0; ob < NB; ob++) {
+      v16f y = zero16();
+#pragma unroll
+      for (int v = 0; v < 4; v++) {
+        const int a = v + 4 * h;
+        y = PG_MFMA(a < A ? th.W3[a * H + 32 * ob + c] : 0.0f, wt[v], y);
+      }
+#pragma unroll
+      for (int v = 0; v < 16; v++) y[v] *= 1.0f - h2[ob][v] * h2[ob][v];
+      g2[ob] = y;
+    }
+    // Three exchanges through the two LDS slots, so that no more than two 128 x 32 activations of the tile are live in registers:
+    // ---- 1. H1 (slot 0, kept to the third exchange) and H2 (slot 1): gW3[a][32 q + j] += sum_s w[s][a] H2[32 q + j][s]
+    wave_put(stage[0][wave], h1, c, h);
+    wave_put(stage[1][wave], h2, c, h);
+    __syncthreads();
+#pragma unroll 1
+    for (int u = 0; u < WAVES; u++) {
+      float ta[16], wa[16];
+#pragma unroll
+      for (int e = 0; e < 16; e++) {
+        const int sm = gs0 + 32 * u + 16 * h + e;   // the sample of k-step e
+        wa[e] = (c < A && sm < n) ? wext[(size_t)sm * A + c] : 0.0f;
+      }
+      wave_get(stage[1][u] + 32 * wave * TP, ta, c, h);
+#pragma unroll
+      for (int s = 0; s < 16; s++) { gW3 = PG_MFMA(wa[s], ta[s], gW3); gb3 += wa[s]; }
+    }
+    // ---- 2. G2 (slot 1): gW2[32 q + i][32 kb + j] += sum_s G2[32 q + i][s] H1[32 kb + j][s]
+    __syncthreads();
+    wave_put(stage[1][wave], g2, c, h);
+    __syncthreads();
+    // G1 = (W2' G2) o (1 - H1^2) of this wavefront's tile (H1 from its slot-0 image): k-step v of block (ob, kb) reads W2[32 kb + r(v, h)][32 ob + c]
+    const float* myh1 = stage[0][wave];
+#pragma unroll
+    for (int ob = 0; ob < NB; ob++) {
+      v16f y = zero16();
+#pragma unroll
+      for (int kb = 0; kb < NB; kb++)
+#pragma unroll
+        for (int v = 0; v < 16; v++) y = PG_MFMA(th.W2[(size_t)(32 * kb + (v & 3) + 8 * (v >> 2) + 4 * h) * H + 32 * ob + c], g2[kb][v], y);
+#pragma unroll
+      for (int v = 0; v < 16; v++) {
+        const float x = myh1[(32 * ob + (v & 3) + 8 * (v >> 2) + 4 * h) * TP + c];
+        y[v] *= 1.0f - x * x;
+      }
+      g1[ob] = y;
+    }
+#pragma unroll 1
+    for (int u = 0; u < WAVES; u++) {
+      float ta[16], tb[16];
+      wave_get(stage[1][u] + 32 * wave * TP, ta, c, h);
+#pragma unroll
+      for (int s = 0; s < 16; s++) gb2 += ta[s];
+#pragma unroll
+      for (int kb = 0; kb < NB; kb++) {
+        wave_get(stage[0][u] + 32 * kb * TP, tb, c, h);
+#pragma unroll
+        for (int s = 0; s < 16; s++) gW2[kb] = PG_MFMA(ta[s], tb[s], gW2[kb]);
+      }
+    }
+    // ---- 3. G1 (slot 0): gW1[32 q + i][k] += sum_s G1[32 q + i][s] [obs | 1][s][k]   (column D: gb1)
+    __syncthreads();
+    wave_put(stage[0][wave], g1, c, h);
+    __syncthreads();
+#pragma unroll 1
+    for (int u = 0; u < WAVES; u++) {
+      float ta[16], xt[16];
+#pragma unroll
+      for (int e = 0; e < 16; e++) {
+        const int sm = gs0 + 32 * u + 16 * h + e;
+        xt[e] = c < D ? (sm < n ? obs[(size_t)sm * D + c] : 0.0f) : (c == D ? 1.0f : 0.0f);
+      }
+      wave_get(stage[0][u] + 32 * wave * TP, ta, c, h);
+#pragma unroll
+      for (int s = 0; s < 16; s++) gW1 = PG_MFMA(ta[s], xt[s], gW1);
+    }
+  }
+  // ---- this workgroup's row: gW[r(v, h)][c] in register v
+  float* out = partial + (size_t)blockIdx.x * S::NP;
+  const int q = wave;
+#pragma unroll
+  for (int v = 0; v < 16; v++) {
+    const int r = (v & 3) + 8 * (v >> 2) + 4 * h;
+#pragma unroll
+    for (int kb = 0; kb < NB; kb++) out[S::O_W2 + (32 * q + r) * H + 32 * kb + c] = gW2[kb][v];
+    if (c < D) out[S::O_W1 + (32 * q + r) * D + c] = gW1[v];
+    if (c == D) out[S::O_B1 + 32 * q + r] = gW1[v];
+    if (r < A) out[S::O_W3 + r * H + 32 * q + c] = gW3[v];
+  }
+  gb2 += __shfl_xor(gb2, 32, 64); gb3 += __shfl_xor(gb3, 32, 64);
+  if (h == 0) out[S::O_B2 + 32 * q + c] = gb2;
+  if (q == 0 && h == 0 && c < A) out[S::O_B3 + c] = gb3;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- Adam
+// Lasagne's adam (lasagne.updates.adam), one lane per parameter: t is the step count AFTER the increment;
+//   a = lr sqrt(1 - beta2^t) / (1 - beta1^t),  m = beta1 m + (1 - beta1) g,  v = beta2 v + (1 - beta2) g^2,  theta -= a m / (sqrt(v) + eps).
+__global__ void __launch_bounds__(256) pg_adam_kernel(int n, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, float* __restrict__ theta,
+                                                      float a, float beta1, float beta2, float eps) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float gi = g[i];
+  const float mi = beta1 * m[i] + (1.0f - beta1) * gi;   // 1 - beta is exact in float32
+  const float vi = beta2 * v[i] + (1.0f - beta2) * (gi * gi);
+  m[i] = mi; v[i] = vi;
+  theta[i] = theta[i] - a * mi / (sqrtf(vi) + eps);
+}
+
+inline int step_blocks(int n) { return ((n + 31) / 32 + WAVES - 1) / WAVES; }
+inline int vjp_blocks(int n) {
+  const int groups = ((n + 31) / 32 + WAVES - 1) / WAVES;
+  return groups < 1 ? 1 : (groups > MAX_VJP_BLOCKS ? MAX_VJP_BLOCKS : groups);
+}
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace cassie_pg
+
+extern "C" {
+
+int CassiePgParamCount(int obs_dim, int act_dim) {
+  if ((obs_dim != 26 && obs_dim != 17) || (act_dim != 6 && act_dim != 7)) return 0;
+  return 128 * obs_dim + 128 + 128 * 128 + 128 + act_dim * 128 + act_dim;
+}
+int CassiePgPartialRows(int n_samples) { return cassie_pg::vjp_blocks(n_samples); }
+
+int CassiePgPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2,
+                       const float* b2, const float* W3, const float* b3, const float* log_std, const float* noise_dev,
+                       const double* low_dev, const double* high_dev, float* obs32_dev, float* mean_dev, float* act_dev,
+                       double* env_actions_dev, void* stream) {
+  using namespace cassie_pg;
+  if (!obs_dev || n <= 0 || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !log_std || !noise_dev || !low_dev || !high_dev || !obs32_dev || !mean_dev ||
+      !act_dev || !env_actions_dev)
+    return CASSIE_EINVAL;
+  if (!aligned16(b1) || !aligned16(W2) || !aligned16(b2) || !aligned16(W3)) return CASSIE_EINVAL;   // read as float4
+  const Net th{W1, b1, W2, b2, W3, b3};
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(step_blocks(n)), block(64 * WAVES);
+  if (obs_dim == 26 && act_dim == 6) hipLaunchKernelGGL((pg_policy_step_kernel<26, 6>), grid, block, 0, s, obs_dev, n, th, log_std, noise_dev, low_dev, high_dev, obs32_dev, mean_dev, act_dev, env_actions_dev);
+  else if (obs_dim == 26 && act_dim == 7) hipLaunchKernelGGL((pg_policy_step_kernel<26, 7>), grid, block, 0, s, obs_dev, n, th, log_std, noise_dev, low_dev, high_dev, obs32_dev, mean_dev, act_dev, env_actions_dev);
+  else return CASSIE_EINVAL;
+  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+}
+
+int CassiePgVjp(const float* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2,
+                const float* W3, const float* b3, const float* w_dev, float* partial_dev, void* stream) {
+  using namespace cassie_pg;
+  if (!obs_dev || n <= 0 || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !w_dev || !partial_dev) return CASSIE_EINVAL;
+  if (!aligned16(b1) || !aligned16(W2) || !aligned16(b2) || !aligned16(W3)) return CASSIE_EINVAL;
+  const Net th{W1, b1, W2, b2, W3, b3};
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(vjp_blocks(n)), block(64 * WAVES);
+  if (obs_dim == 26 && act_dim == 6) hipLaunchKernelGGL((pg_vjp_kernel<26, 6>), grid, block, 0, s, obs_dev, n, th, w_dev, partial_dev);
+  else if (obs_dim == 26 && act_dim == 7) hipLaunchKernelGGL((pg_vjp_kernel<26, 7>), grid, block, 0, s, obs_dev, n, th, w_dev, partial_dev);
+  else if (obs_dim == 17 && act_dim == 6) hipLaunchKernelGGL((pg_vjp_kernel<17, 6>), grid, block, 0, s, obs_dev, n, th, w_dev, partial_dev);
+  else if (obs_dim == 17 && act_dim == 7) hipLaunchKernelGGL((pg_vjp_kernel<17, 7>), grid, block, 0, s, obs_dev, n, th, w_dev, partial_dev);
+  else return CASSIE_EINVAL;
+  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+}
+
+int CassiePgAdam(int n, const float* g, float* m, float* v, float* theta, int t, float lr, float beta1, float beta2, float eps, void* stream) {
+  if (n <= 0 || !g || !m || !v || !theta || t < 1) return CASSIE_EINVAL;
+  const double a = (double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t));
+  hipLaunchKernelGGL(cassie_pg::pg_adam_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, g, m, v, theta, (float)a, beta1, beta2, eps);
+  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+}
+
+}  // extern "C"

@@ -872,9 +872,18 @@ class TRPO:
                   path_t=self.path_t.cpu(), path_ret=self.path_ret.cpu(), steps_to_trunc=int(self._steps_to_trunc),
                   env_state=None if env is None or not hasattr(env, "get_full_state_host") else torch.from_numpy(env.get_full_state_host()),
                   terrain=terrain_lib.spec_key(getattr(self, "terrain_spec", None)))
+        ck.update(self._snapshot_fields())
         mine = self._rank_path(path)
         torch.save(ck, mine + ".tmp")
         os.replace(mine + ".tmp", mine)
+
+    def _snapshot_fields(self):
+        """Entries a subclass adds to the snapshot (its optimiser state); TRPO has none."""
+        return {}
+
+    def _load_fields(self, ck):
+        """Called with the loaded snapshot before anything is restored: a subclass refuses a snapshot that is not its own and takes
+        back its _snapshot_fields().  TRPO has none."""
 
     def load(self, path, restore_sampler=True):
         """Returns (extra, sampler_restored): policy / baseline / iteration always come back; the sampler state (env records,
@@ -884,6 +893,7 @@ class TRPO:
         dev = next(self.policy.parameters()).device
         mine = self._rank_path(path)
         ck = torch.load(mine if os.path.exists(mine) else path, map_location="cpu", weights_only=True)
+        self._load_fields(ck)
         # the ground is part of the run: resuming on other terrain would silently be a different run (snapshots without the key: flat floor)
         mine_spec, theirs = terrain_lib.spec_key(getattr(self, "terrain_spec", None)), ck.get("terrain")
         if mine_spec != theirs:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Counterpart of rllab/envs/sim_policy.py:19-31 on the batched MI355X environment: load a snapshot written by train_trpo.py
-(`--snapshot`, snapshot_mode="last") and roll the policy out -- no training.  The reference animates ONE env through rllab's
+"""Counterpart of rllab/envs/sim_policy.py:19-31 on the batched MI355X environment: load a snapshot written by train_trpo.py or
+train_vpg.py (`--snapshot`, snapshot_mode="last"; a VPG snapshot carries its policy's hidden sizes) and roll the policy out -- no training.  The reference animates ONE env through rllab's
 `rollout(env, policy, max_path_length, animated=True)`; here N resident envs run the same loop in parallel (there is no
 viewer: GUI is out of scope) and the script prints what the reference's loop would let one read off the screen: path
 lengths and returns.
@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("file", help="snapshot written by train_trpo.py --snapshot")
+    ap.add_argument("file", help="snapshot written by train_trpo.py or train_vpg.py --snapshot")
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--max-path-length", type=int, default=1000)   # sim_policy.py:14 default
     ap.add_argument("--kind", default="walk", choices=["walk", "stand"])
@@ -36,8 +36,15 @@ def main():
     from cassierl_amd.trpo import make_cassie_trpo
     from cassierl_amd.terrain import terrain_spec
     terrain = terrain_spec(args.terrain_dir, args.num_terrains, args.terrain_elevation, args.terrain_seed) if args.terrain_dir else None
-    algo = make_cassie_trpo(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
-                            terrain=terrain)
+    ck = torch.load(args.file, map_location="cpu", weights_only=True)
+    if ck.get("algo") == "vpg":   # a train_vpg.py snapshot: the policy's shape comes from it
+        from cassierl_amd.vpg import make_cassie_vpg
+        algo = make_cassie_vpg(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
+                               terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (32, 32))))
+    else:
+        algo = make_cassie_trpo(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
+                                terrain=terrain)
+    del ck
     _, _ = algo.load(args.file, restore_sampler=False)   # policy + baseline only: every path starts from env.reset()
     pol, n = algo.policy, args.envs
     dt = next(pol.parameters()).dtype
