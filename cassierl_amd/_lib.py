@@ -32,6 +32,7 @@ EXPORTS = [
     "CassieTrpoBaselineFeatures", "CassieTrpoBaselinePredict", "CassieTrpoReturnsAdvantages", "CassieTrpoGramRows", "CassieTrpoGramRowSize", "CassieTrpoBaselineGram", "CassieTrpoRidgeSolve",
     # width-128 policy (include/cassie_trpo.h)
     "CassiePgParamCount", "CassiePgPolicyStep", "CassiePgPartialRows", "CassiePgVjp", "CassiePgAdam",
+    "CassiePgFvp", "CassiePgSurrogateRows", "CassiePgSurrogate", "CassiePgCgUpdate",
 ]
 
 

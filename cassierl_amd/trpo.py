@@ -122,6 +122,11 @@ class GaussianMLPPolicy(nn.Module):
         return (num / (2 * new_std ** 2 + 1e-8) + new_log_std - old_log_std).sum(-1)
 
 
+def hidden_sizes_of(policy):
+    """Hidden layer widths of a GaussianMLPPolicy, e.g. (128, 128)."""
+    return tuple(m.out_features for m in policy.mean_net if isinstance(m, nn.Linear))[:-1]
+
+
 def gram(X, y, chunk=2048):
     """(X'X, X'y) for a tall-skinny X [N, F].  One GEMM with K = N is pathological in rocBLAS (56 ms for 524 288 x 58 in
     FP64 on MI355X); a batch of K = `chunk` GEMMs summed afterwards does the same arithmetic in 0.2 ms."""
@@ -336,6 +341,7 @@ class AnalyticFisher:
     backprop through mean-KL): F v = (1/N) J' S J v for the mean network (J = d mean / d theta by forward mode, S the
     precision of the old Gaussian) plus a diagonal block for log_std.  Activations of the OLD policy are computed once per
     TRPO update; a product is then ~8 GEMMs and a handful of element-wise kernels instead of ~100 autograd kernels."""
+    kind = "analytic"
 
     def __init__(self, policy, obs, eps=1e-8):
         lin = [m for m in policy.mean_net if isinstance(m, nn.Linear)]
@@ -397,21 +403,25 @@ class FusedFisher:
     """The same Fisher-vector products as AnalyticFisher, each in ONE launch of the fused HIP kernel (csrc/tu_trpo.hip,
     include/cassie_trpo.h): forward mode along the direction, precision of the old Gaussian, reverse mode and the outer-product
     accumulation per wavefront; obs is the only per-sample tensor read.  `vjp(w)` gives J' w for per-sample cotangents (the policy
-    gradient).  CUDA float32 policies of the supported shapes only (ValueError otherwise: the caller falls back to AnalyticFisher)."""
+    gradient).  CUDA float32 policies of the supported shapes only (ValueError otherwise: the caller falls back to AnalyticFisher).
+    PgFisher is the same object for the 128 x 128 policy: it swaps the entry points (_bind) and the hidden width."""
+    kind, hidden = "trpo_fvp", 32
 
     def __init__(self, policy, obs, eps=1e-8):
         import ctypes as ct
         from . import _lib
+        name, H = type(self).__name__, self.hidden
         lin = [m for m in policy.mean_net if isinstance(m, nn.Linear)]
         if len(lin) != 3 or not all(isinstance(m, (nn.Linear, nn.Tanh)) for m in policy.mean_net):
-            raise ValueError("FusedFisher covers the two-hidden-layer tanh policy of trpo_cassie.py only")
-        if not obs.is_cuda or obs.dtype != torch.float32 or lin[0].out_features != 32 or lin[1].out_features != 32:
-            raise ValueError("FusedFisher needs a float32 CUDA batch and 32 x 32 hidden units")
+            raise ValueError("%s covers the two-hidden-layer tanh policy of trpo_cassie.py only" % name)
+        if not obs.is_cuda or obs.dtype != torch.float32 or lin[0].out_features != H or lin[1].out_features != H:
+            raise ValueError("%s needs a float32 CUDA batch and %d x %d hidden units" % (name, H, H))
         self.L = _lib.load()
+        self._bind()
         self.D, self.A = lin[0].in_features, lin[2].out_features
-        self.NP = self.L.CassieTrpoParamCount(self.D, self.A)
+        self.NP = self._param_count(self.D, self.A)
         if self.NP == 0:
-            raise ValueError("FusedFisher: unsupported policy shape %d -> %d" % (self.D, self.A))
+            raise ValueError("%s: unsupported policy shape %d -> %d" % (name, self.D, self.A))
         self.ct = ct
         self.obs = obs.contiguous()
         self.n = obs.shape[0]
@@ -423,10 +433,23 @@ class FusedFisher:
             var = (2 * policy.log_std.detach()).exp()
             self.prec = (2.0 / (2.0 * var + eps)).to(torch.float32).contiguous()
             self.h_ls = 4.0 * var * (2.0 * var - eps) / (2.0 * var + eps) ** 2
-        self.rows = self.L.CassieTrpoPartialRows(self.n)
+        self.rows = self._partial_rows(self.n)
         self.partial = torch.empty((self.rows, self.NP), dtype=torch.float32, device=obs.device)
         # offsets of the kernel's row layout [gW1 | gb1 | gW2 | gb2 | gW3 | gb3]
-        self.sizes = [32 * self.D, 32, 1024, 32, self.A * 32, self.A]
+        self.sizes = [H * self.D, H, H * H, H, self.A * H, self.A]
+
+    def _bind(self):
+        """The width-32 entry points (csrc/tu_trpo.hip)."""
+        L = self.L
+        self._param_count, self._partial_rows, self._sur_rows = L.CassieTrpoParamCount, L.CassieTrpoPartialRows, L.CassieTrpoPartialRows
+        self._vjp_entry, self._sur_entry, self._cg_entry = L.CassieTrpoVjp, L.CassieTrpoSurrogate, L.CassieTrpoCgUpdate
+
+    def _fvp(self, parts, stream):
+        """The mean network's F v for this rank's samples into self.partial (one row per wavefront)."""
+        rc = self.L.CassieTrpoFvp(self.ct.c_void_p(self.obs.data_ptr()), self.n, self.D, self.A, *self._ptrs(self.theta), *self._ptrs(parts),
+                                  self.ct.c_void_p(self.prec.data_ptr()), self.ct.c_float(1.0 / self.n), self.ct.c_void_p(self.partial.data_ptr()), stream)
+        if rc != 0:
+            raise RuntimeError("CassieTrpoFvp failed (%d)" % rc)
 
     def _split(self, v):
         parts, i = {}, 0
@@ -450,22 +473,14 @@ class FusedFisher:
     def __call__(self, v):
         v = v.to(torch.float32).contiguous()
         parts = self._split(v)
-        stream = self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream)
-        rc = self.L.CassieTrpoFvp(self.ct.c_void_p(self.obs.data_ptr()), self.n, self.D, self.A, *self._ptrs(self.theta), *self._ptrs(parts),
-                                  self.ct.c_void_p(self.prec.data_ptr()), self.ct.c_float(1.0 / self.n), self.ct.c_void_p(self.partial.data_ptr()), stream)
-        if rc != 0:
-            raise RuntimeError("CassieTrpoFvp failed (%d)" % rc)
+        self._fvp(parts, self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream))
         return self._assemble(self.partial.sum(0), self.h_ls * parts["log_std"])
 
     @torch.no_grad()
     def mean_product(self, v):
         """The mean network's part of F v for this rank's samples, [NP] float32 in the kernel's order (no log_std block, no damping)."""
         parts = self._split(v)
-        stream = self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream)
-        rc = self.L.CassieTrpoFvp(self.ct.c_void_p(self.obs.data_ptr()), self.n, self.D, self.A, *self._ptrs(self.theta), *self._ptrs(parts),
-                                  self.ct.c_void_p(self.prec.data_ptr()), self.ct.c_float(1.0 / self.n), self.ct.c_void_p(self.partial.data_ptr()), stream)
-        if rc != 0:
-            raise RuntimeError("CassieTrpoFvp failed (%d)" % rc)
+        self._fvp(parts, self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream))
         return self.partial.sum(0)
 
     @torch.no_grad()
@@ -488,10 +503,10 @@ class FusedFisher:
         P = lambda t: self.ct.c_void_p(t.data_ptr())
         for _ in range(iters):
             apm = all_mean_(self.mean_product(p), "fvp_all_reduce")
-            rc = self.L.CassieTrpoCgUpdate(n, ls_off, self.A, P(apm), P(hls), self.ct.c_float(reg), self.ct.c_float(tol), P(x), P(r), P(p), P(scal),
-                                           self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream))
+            rc = self._cg_entry(n, ls_off, self.A, P(apm), P(hls), self.ct.c_float(reg), self.ct.c_float(tol), P(x), P(r), P(p), P(scal),
+                                self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream))
             if rc != 0:
-                raise RuntimeError("CassieTrpoCgUpdate failed (%d)" % rc)
+                raise RuntimeError("%s failed (%d)" % (self._cg_entry.__name__, rc))
         return x
 
     @torch.no_grad()
@@ -499,10 +514,10 @@ class FusedFisher:
         """J' w for w [n, act_dim] float32 (cotangents on the mean); the log_std slot of the result is zero."""
         w = w.to(torch.float32).contiguous()
         stream = self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream)
-        rc = self.L.CassieTrpoVjp(self.ct.c_void_p(self.obs.data_ptr()), self.n, self.D, self.A, *self._ptrs(self.theta),
-                                  self.ct.c_void_p(w.data_ptr()), self.ct.c_void_p(self.partial.data_ptr()), stream)
+        rc = self._vjp_entry(self.ct.c_void_p(self.obs.data_ptr()), self.n, self.D, self.A, *self._ptrs(self.theta),
+                             self.ct.c_void_p(w.data_ptr()), self.ct.c_void_p(self.partial.data_ptr()), stream)
         if rc != 0:
-            raise RuntimeError("CassieTrpoVjp failed (%d)" % rc)
+            raise RuntimeError("%s failed (%d)" % (self._vjp_entry.__name__, rc))
         return self._assemble(self.partial.sum(0), torch.zeros_like(self.theta["log_std"]))
 
     @torch.no_grad()
@@ -511,17 +526,40 @@ class FusedFisher:
         the line search's evaluation.  old_log_std: the [act_dim] vector of the state-independent old log-std.  Two float64 scalars on the device."""
         live = dict(policy.named_parameters())
         if not hasattr(self, "_sur"):
-            self._sur = torch.empty((self.rows, 2), dtype=torch.float64, device=self.obs.device)
+            self._sur = torch.empty((self._sur_rows(self.n), 2), dtype=torch.float64, device=self.obs.device)
         P = lambda t: self.ct.c_void_p(t.data_ptr())
         act, adv, old_mean = act.contiguous(), adv.to(torch.float32).contiguous(), old_mean.contiguous()
         old_ls = old_log_std.to(torch.float32).contiguous()
         stream = self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream)
-        rc = self.L.CassieTrpoSurrogate(P(self.obs), self.n, self.D, self.A, *[P(live[k].detach()) for k in self.order], P(live["log_std"].detach()), P(old_ls),
-                                        P(act), P(adv), P(old_mean), P(self._sur), stream)
+        rc = self._sur_entry(P(self.obs), self.n, self.D, self.A, *[P(live[k].detach()) for k in self.order], P(live["log_std"].detach()), P(old_ls),
+                             P(act), P(adv), P(old_mean), P(self._sur), stream)
         if rc != 0:
-            raise RuntimeError("CassieTrpoSurrogate failed (%d)" % rc)
+            raise RuntimeError("%s failed (%d)" % (self._sur_entry.__name__, rc))
         s = self._sur.sum(0) / self.n
         return s[0], s[1]
+
+
+class PgFisher(FusedFisher):
+    """FusedFisher for the 128 x 128 policy (csrc/tu_pg_trpo.hip): the product is CassiePgFvp (forward mode into a [n, act_dim] cotangent,
+    then CassiePgVjp), the CG step CassiePgCgUpdate, the line search CassiePgSurrogate and the gradient CassiePgVjp.  Same interface."""
+    kind, hidden = "pg_fvp", 128
+
+    def _bind(self):
+        L = self.L
+        self._param_count, self._partial_rows, self._sur_rows = L.CassiePgParamCount, L.CassiePgPartialRows, L.CassiePgSurrogateRows
+        self._vjp_entry, self._sur_entry, self._cg_entry = L.CassiePgVjp, L.CassiePgSurrogate, L.CassiePgCgUpdate
+
+    def _fvp(self, parts, stream):
+        if not hasattr(self, "_work"):
+            self._work = torch.empty((self.n, self.A), dtype=torch.float32, device=self.obs.device)
+        # the kernel reads db1, dW2, db2, dW3 as float4: in the flat parameter vector they sit behind log_std (act_dim floats), so the
+        # direction's mean-network part is copied into a fresh buffer, where every block starts on a 16-byte boundary
+        direction = dict(zip(self.order, torch.split(torch.cat([parts[k].reshape(-1) for k in self.order]), self.sizes)))
+        rc = self.L.CassiePgFvp(self.ct.c_void_p(self.obs.data_ptr()), self.n, self.D, self.A, *self._ptrs(self.theta), *self._ptrs(direction),
+                                self.ct.c_void_p(self.prec.data_ptr()), self.ct.c_float(1.0 / self.n), self.ct.c_void_p(self._work.data_ptr()),
+                                self.ct.c_void_p(self.partial.data_ptr()), stream)
+        if rc != 0:
+            raise RuntimeError("CassiePgFvp failed (%d)" % rc)
 
 
 # --------------------------------------------------------------------------------------------- TRPO
@@ -567,15 +605,17 @@ class TRPO:
         self.itr = 0
 
     def _fused_policy_step(self, dev, pol_dtype):
-        """The fused policy-step launcher (include/cassie_trpo.h: CassieTrpoPolicyStep) when it applies -- CUDA, float32 two-layer
-        tanh policy of a supported shape, rllab's normalize() action map -- else None (the torch operations below)."""
+        """The fused policy-step launcher (include/cassie_trpo.h: CassieTrpoPolicyStep for 32 x 32 hidden units, CassiePgPolicyStep for
+        128 x 128) when it applies -- CUDA, float32 two-layer tanh policy of a supported shape, rllab's normalize() action map -- else None
+        (the torch operations below)."""
         if not getattr(self, "fused_policy_step", True) or dev.type != "cuda" or pol_dtype != torch.float32 or not isinstance(self.act_map, NormalizedActions):
             return None
         lin = [m for m in self.policy.mean_net if isinstance(m, nn.Linear)]
         if len(lin) != 3 or not all(isinstance(m, (nn.Linear, nn.Tanh)) for m in self.policy.mean_net):
             return None
         D, A = lin[0].in_features, lin[2].out_features
-        if (D, A) not in ((26, 6), (26, 7)) or lin[0].out_features != 32 or lin[1].out_features != 32 or self.obs_dim != D:
+        entry = {(32, 32): "CassieTrpoPolicyStep", (128, 128): "CassiePgPolicyStep"}.get((lin[0].out_features, lin[1].out_features))
+        if (D, A) not in ((26, 6), (26, 7)) or entry is None or self.obs_dim != D:
             return None
         try:
             import ctypes as ct
@@ -592,14 +632,17 @@ class TRPO:
         if not all(t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == A for t in (low, high)):
             return None
 
+        fn = getattr(L, entry)
+        self.policy_step_entry = entry
+
         def step(obs, noise, obs32, mean, act):
             if obs.dtype != torch.float64 or not obs.is_contiguous():
-                raise TypeError("CassieTrpoPolicyStep: observations must be a contiguous float64 tensor (got %s)" % obs.dtype)
+                raise TypeError("%s: observations must be a contiguous float64 tensor (got %s)" % (entry, obs.dtype))
             assert noise.is_contiguous() and obs32.is_contiguous()
-            rc = L.CassieTrpoPolicyStep(P(obs), n, D, A, *w, P(noise), P(low), P(high), P(obs32), P(mean), P(act), P(self._env_actions),
-                                        ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = fn(P(obs), n, D, A, *w, P(noise), P(low), P(high), P(obs32), P(mean), P(act), P(self._env_actions),
+                    ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
             if rc != 0:
-                raise RuntimeError("CassieTrpoPolicyStep failed (%d)" % rc)
+                raise RuntimeError("%s failed (%d)" % (entry, rc))
         return step
 
     def _fused_sampler_step(self, dev):
@@ -749,17 +792,19 @@ class TRPO:
 
         # Fisher-vector products: closed form for the tanh-MLP Gaussian policy -- FusedFisher = the product as ONE launch on the matrix
         # cores (csrc/tu_trpo.hip: 0.16 ms against 0.66 ms per product for the torch operations of AnalyticFisher at 524 288 samples,
-        # r04), AnalyticFisher where the kernel does not apply (CPU, other shapes); otherwise double backprop through ONE graph of
-        # grad(KL) (the KL and its gradient do not depend on v: only the second backward pass is repeated per product)
+        # r04), PgFisher its counterpart for the 128 x 128 policy (csrc/tu_pg_trpo.hip), AnalyticFisher where no kernel applies (CPU, other
+        # shapes); otherwise double backprop through ONE graph of grad(KL) (the KL and its gradient do not depend on v: only the second
+        # backward pass is repeated per product).  last_fisher_kind says which ran: "trpo_fvp", "pg_fvp", "analytic" or "autograd".
         gk = kl0 = None
         fisher = None
         if getattr(self, "analytic_fisher", True):
-            for cls in ((FusedFisher, AnalyticFisher) if getattr(self, "fused_fisher", True) else (AnalyticFisher,)):
+            for cls in ((FusedFisher, PgFisher, AnalyticFisher) if getattr(self, "fused_fisher", True) else (AnalyticFisher,)):
                 try:
                     fisher = cls(pol, obs)
                     break
                 except (ValueError, OSError):
                     fisher = None
+        self.last_fisher_kind = "autograd" if fisher is None else fisher.kind
         if fisher is not None:
             # policy gradient in closed form too: at theta = theta_old the likelihood ratio is 1, so with z = (a - mean) / std
             #   d loss / d mean = -adv z / std / N,   d loss / d log_std = -sum_s adv (z^2 - 1) / N,   loss = -mean(adv)
@@ -794,7 +839,7 @@ class TRPO:
         if descent is None:
             descent = conjugate_gradient(Fvp, g, self.cg_iters)
         shs = 0.5 * (descent @ Fvp(descent))
-        if isinstance(fisher, FusedFisher):   # the line search evaluates loss and KL in one launch each (CassieTrpoSurrogate)
+        if isinstance(fisher, FusedFisher):   # the line search evaluates loss and KL in one launch each (CassieTrpoSurrogate / CassiePgSurrogate)
             ff, old_ls_vec = fisher, old_lstd[0].detach().clone()
             surrogate = lambda: ff.surrogate(pol, act, adv, old_mean, old_ls_vec)
         del gk, kl0, fisher
@@ -878,12 +923,15 @@ class TRPO:
         os.replace(mine + ".tmp", mine)
 
     def _snapshot_fields(self):
-        """Entries a subclass adds to the snapshot (its optimiser state); TRPO has none."""
-        return {}
+        """Entries of the snapshot beyond the common ones (a subclass adds its optimiser state): TRPO records the policy's hidden sizes."""
+        return dict(hidden_sizes=list(hidden_sizes_of(self.policy)))
 
     def _load_fields(self, ck):
-        """Called with the loaded snapshot before anything is restored: a subclass refuses a snapshot that is not its own and takes
-        back its _snapshot_fields().  TRPO has none."""
+        """Called with the loaded snapshot before anything is restored: refuses a snapshot that is not this run's (a subclass also takes
+        back its _snapshot_fields()).  TRPO: the policy's hidden sizes must match (a snapshot without them was written by a 32 x 32 run)."""
+        theirs, mine = tuple(ck.get("hidden_sizes", (32, 32))), hidden_sizes_of(self.policy)
+        if theirs != mine:
+            raise ValueError("TRPO.load: the snapshot's policy has hidden sizes %r, this run's has %r" % (theirs, mine))
 
     def load(self, path, restore_sampler=True):
         """Returns (extra, sampler_restored): policy / baseline / iteration always come back; the sampler state (env records,
@@ -930,11 +978,13 @@ def broadcast_initial_policy(algo):
         set_flat_params(algo.policy, theta)
 
 
-def make_cassie_trpo(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, sync_policy=True, terrain=None, **kw):
+def make_cassie_trpo(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, sync_policy=True, terrain=None, hidden_sizes=(32, 32),
+                     init_std=2.0, **kw):
     """trpo_cassie.py:12-42 on the batched MI355X environment.  sync_policy=False: NOTHING collective happens in here (the env, its workspaces, the
     policy are local allocations that can fail on one rank alone); the caller agrees on success across ranks first and then calls
     broadcast_initial_policy(algo) (bench.py's TRPO stage).  terrain: None (the flat floor) or a spec of terrain.terrain_spec -- every
-    environment on its own field of the spec's library, drawn by terrain.assign_terrains over the GLOBAL env ids; snapshots record it."""
+    environment on its own field of the spec's library, drawn by terrain.assign_terrains over the GLOBAL env ids; snapshots record it.
+    hidden_sizes / init_std: the policy (trpo_cassie.py's 32 x 32 and 2.0 by default; (128, 128) runs on the kernels of csrc/tu_pg*.hip)."""
     from .vec_env import CassieVecEnv
     env = CassieVecEnv(n_envs, kind=kind, control_mode=control_mode, n_substeps=10, auto_reset=True, device=device, trajectory=trajectory)
     env.use_torch_stream()
@@ -942,7 +992,7 @@ def make_cassie_trpo(n_envs, kind="walk", control_mode="PD", device=0, trajector
     bufs = env.alloc()
     torch.manual_seed(seed)  # trpo_cassie.py:53 seed=1: every rank builds the same initial policy ...
     obs_w = env.observation_space.shape[0]  # what step() emits (26 for both kinds); the policy is sized from the env, as trpo_cassie.py does through env.spec
-    policy = GaussianMLPPolicy(obs_w, env.adim, (32, 32), init_std=2.0).to(dev)
+    policy = GaussianMLPPolicy(obs_w, env.adim, tuple(hidden_sizes), init_std=init_std).to(dev)
     act_map = NormalizedActions(env.action_space.low, env.action_space.high, dev)
     algo = TRPO(lambda a: env.step(a, bufs), lambda: env.reset(bufs), policy, LinearFeatureBaseline(), n_envs, obs_w, act_map, seed=seed,
                 env_reset_masked=lambda m: env.reset(bufs, mask=m), **kw)

@@ -27,14 +27,9 @@ from torch import nn
 
 from . import terrain as terrain_lib
 from .trpo import (TRPO, FusedFisher, GaussianMLPPolicy, LinearFeatureBaseline, NormalizedActions, _world, all_mean_, broadcast_initial_policy,
-                   flat_grad, flat_params, set_flat_params)
+                   flat_grad, flat_params, hidden_sizes_of, set_flat_params)
 
 _MEAN_ORDER = ["mean_net.0.weight", "mean_net.0.bias", "mean_net.2.weight", "mean_net.2.bias", "mean_net.4.weight", "mean_net.4.bias"]
-
-
-def hidden_sizes_of(policy):
-    """Hidden layer widths of a GaussianMLPPolicy, e.g. (128, 128)."""
-    return tuple(m.out_features for m in policy.mean_net if isinstance(m, nn.Linear))[:-1]
 
 
 def _two_layer_tanh(policy):
@@ -157,38 +152,7 @@ class VPG(TRPO):
     def hidden_sizes(self):
         return hidden_sizes_of(self.policy)
 
-    def _fused_policy_step(self, dev, pol_dtype):
-        """CassiePgPolicyStep for a 128-128 policy; every other shape is TRPO's decision (the width-32 kernel or the torch operations)."""
-        if self.hidden_sizes != (128, 128):
-            return super()._fused_policy_step(dev, pol_dtype)
-        if not getattr(self, "fused_policy_step", True) or dev.type != "cuda" or pol_dtype != torch.float32 or not isinstance(self.act_map, NormalizedActions):
-            return None
-        lin = _two_layer_tanh(self.policy)
-        if lin is None:
-            return None
-        D, A = lin[0].in_features, lin[2].out_features
-        if (D, A) not in ((26, 6), (26, 7)) or self.obs_dim != D:
-            return None
-        low, high, n = self.act_map.low, self.act_map.high, self.n_envs
-        if not all(t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == A for t in (low, high)):
-            return None
-        import ctypes as ct
-        from . import _lib
-        L = _lib.load()
-        if not hasattr(self, "_env_actions") or self._env_actions.shape != (n, A):
-            self._env_actions = torch.empty((n, A), dtype=torch.float64, device=dev)
-        P = lambda t: ct.c_void_p(t.data_ptr())
-        w = [P(lin[0].weight), P(lin[0].bias), P(lin[1].weight), P(lin[1].bias), P(lin[2].weight), P(lin[2].bias), P(self.policy.log_std)]
-
-        def step(obs, noise, obs32, mean, act):
-            if obs.dtype != torch.float64 or not obs.is_contiguous():
-                raise TypeError("CassiePgPolicyStep: observations must be a contiguous float64 tensor (got %s)" % obs.dtype)
-            assert noise.is_contiguous() and obs32.is_contiguous()
-            rc = L.CassiePgPolicyStep(P(obs), n, D, A, *w, P(noise), P(low), P(high), P(obs32), P(mean), P(act), P(self._env_actions),
-                                      ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if rc != 0:
-                raise RuntimeError("CassiePgPolicyStep failed (%d)" % rc)
-        return step
+    # the sampler's policy step (CassiePgPolicyStep for a 128-128 policy, CassieTrpoPolicyStep for 32 x 32) is TRPO._fused_policy_step
 
     def optimize(self, d):
         pol = self.policy

@@ -123,6 +123,30 @@ int CassiePgVjp(const float* obs_dev, int n, int obs_dim, int act_dim, const flo
  * (eps outside the bias correction, unlike torch.optim.Adam). */
 int CassiePgAdam(int n, const float* g, float* m, float* v, float* theta, int t, float lr, float beta1, float beta2, float eps, void* stream);
 
+/* TRPO for the 128-128 network (csrc/tu_pg_trpo.hip).  Shapes: obs_dim 26 or 17, act_dim 6 or 7 (CASSIE_EINVAL otherwise); the direction's
+ * db1, dW2, db2 and dW3 must be 16-byte aligned as the weights are. */
+
+/* CassieTrpoFvp's contract for the 128-128 network: (scale) J' S J v with J at the current weights, S = diag(prec[act_dim]) and the direction
+ * dW1..db3, into partial [CassiePgPartialRows(n)][CassiePgParamCount] (rows [gW1 | gb1 | gW2 | gb2 | gW3 | gb3], added by the caller).  Two
+ * launches on `stream`: forward mode writes w = scale * prec * (J v) into work_dev [n][act_dim] (caller-owned, n * act_dim floats), then
+ * CassiePgVjp takes J' w. */
+int CassiePgFvp(const float* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2,
+                const float* W3, const float* b3, const float* dW1, const float* db1, const float* dW2, const float* db2, const float* dW3,
+                const float* db3, const float* prec, float scale, float* work_dev, float* partial_dev, void* stream);
+
+/* CassieTrpoSurrogate's contract for the 128-128 network: partial [CassiePgSurrogateRows(n)][2] float64, per row
+ * (sum_s -exp(ll_new - ll_old) adv_s, sum_s KL(old_s || new_s)), one row per workgroup of 128 samples; the caller adds the rows and
+ * divides by the job's n. */
+int CassiePgSurrogateRows(int n_samples);
+int CassiePgSurrogate(const float* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2,
+                      const float* W3, const float* b3, const float* log_std_new, const float* log_std_old, const float* act_dev,
+                      const float* adv_dev, const float* old_mean_dev, double* partial_dev, void* stream);
+
+/* CassieTrpoCgUpdate's semantics (early exit once rr' < tol, the log_std block at ls_off, reg damping) for n <= 21 504 (the 128-128
+ * network has CassiePgParamCount(26, 7) + 7 = 20 878 parameters), one launch; dot products in a fixed order. */
+int CassiePgCgUpdate(int n, int ls_off, int n_ls, const float* Ap_mean_dev, const float* hls_dev, float reg, float tol, float* x_dev, float* r_dev, float* p_dev,
+                     float* scal_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

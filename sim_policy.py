@@ -41,9 +41,9 @@ def main():
         from cassierl_amd.vpg import make_cassie_vpg
         algo = make_cassie_vpg(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
                                terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (32, 32))))
-    else:
+    else:   # a train_trpo.py snapshot: 32 x 32 unless it records other hidden sizes
         algo = make_cassie_trpo(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
-                                terrain=terrain)
+                                terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (32, 32))))
     del ck
     _, _ = algo.load(args.file, restore_sampler=False)   # policy + baseline only: every path starts from env.reset()
     pol, n = algo.policy, args.envs

@@ -4,6 +4,7 @@
 
 Hyper-parameters are those of trpo_cassie.py:21-42 (MLP 32x32, init_std 2.0, discount 0.99, step_size 0.005,
 max_path_length 1000); batch_size defaults to one Env.step of every environment per iteration times --horizon.
+--hidden 128,128 (with --init-std 1.0: vpg_cassie.py's policy) trains the wide policy on its own kernels (csrc/tu_pg_trpo.hip).
 """
 import argparse
 import json
@@ -17,7 +18,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs-per-gpu", type=int, default=4096)
     ap.add_argument("--horizon", type=int, default=4, help="Env.steps per environment per iteration")
@@ -32,7 +33,13 @@ def main():
     ap.add_argument("--terrain-elevation", type=float, default=1.0, help="height of a white pixel in metres (the <hfield> size_z)")
     ap.add_argument("--terrain-seed", type=int, default=1, help="seed of the file draw and of the per-environment field ids")
     ap.add_argument("--dump-params", default="", help="rank 0 writes the flat policy parameters (.npy) after the last iteration")
-    args = ap.parse_args()
+    ap.add_argument("--hidden", default="32,32", help="hidden layer widths of the Gaussian MLP policy (32,32 and 128,128 run on HIP kernels)")
+    ap.add_argument("--init-std", type=float, default=2.0)
+    return ap
+
+
+def main():
+    args = parser().parse_args()
     import torch
     from cassierl_amd import rollout as R
     from cassierl_amd.trajectory import default_gait
@@ -43,8 +50,10 @@ def main():
     traj = default_gait()
     from cassierl_amd.terrain import terrain_spec
     terrain = terrain_spec(args.terrain_dir, args.num_terrains, args.terrain_elevation, args.terrain_seed) if args.terrain_dir else None
+    hidden = tuple(int(x) for x in args.hidden.split(","))
     algo = make_cassie_trpo(args.envs_per_gpu, kind=args.kind, control_mode=args.control_mode, device=dev,
-                            trajectory=traj, seed=1, batch_size=args.envs_per_gpu * world * args.horizon, terrain=terrain)
+                            trajectory=traj, seed=1, batch_size=args.envs_per_gpu * world * args.horizon, terrain=terrain,
+                            hidden_sizes=hidden, init_std=args.init_std)
     algo.timing = args.timing
     if args.load_policy:
         _, restored = algo.load(args.load_policy)
