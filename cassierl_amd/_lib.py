@@ -33,6 +33,8 @@ EXPORTS = [
     # width-128 policy (include/cassie_trpo.h)
     "CassiePgParamCount", "CassiePgPolicyStep", "CassiePgPartialRows", "CassiePgVjp", "CassiePgAdam",
     "CassiePgFvp", "CassiePgSurrogateRows", "CassiePgSurrogate", "CassiePgCgUpdate",
+    # DDPG (include/cassie_trpo.h)
+    "CassieDdpgParamCount", "CassieDdpgPartialRows", "CassieDdpgPolicyStep", "CassieDdpgPoolCommit", "CassieDdpgCriticGrad", "CassieDdpgActorGrad", "CassieDdpgApply",
 ]
 
 

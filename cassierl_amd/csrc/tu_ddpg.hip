@@ -1,0 +1,677 @@
+// tu_ddpg.hip -- fused kernels of DDPG (include/cassie_trpo.h, cassierl_amd/ddpg.py; rllab/envs/ddpg_cassie.py): the policy step that
+// writes straight into the replay pool, the pool commit after Env.step, the critic's and the actor's gradient on a batch gathered from the
+// pool by index, and the Adam step + soft target update.  One update is four launches (critic gradient, apply, actor gradient, apply)
+// where the torch statement (ddpg.ddpg_update_torch_) is 60 or more.
+//
+// The networks are 32 x 32 with ReLU hidden units:
+//   actor   mu(s) = tanh(W3 relu(W2 relu(W1 s + b1) + b2) + b3)          W1 [32][D], W2 [32][32], W3 [A][32]
+//   critic  Q(s, a) = W3 relu(W2 [relu(W1 s + b1); a] + b2) + b3          W1 [32][D], W2 [32][32 + A], W3 [1][32]
+// and the layout is tu_trpo.hip's (read its header first): exact float32 v_mfma_f32_32x32x2_f32, a tile of 32 samples per wavefront, every
+// activation in the accumulator layout (sample on the lane c = lane & 31, hidden unit r(v, h) = (v & 3) + 8 (v >> 2) + 4 h in register v),
+// the A operands of every product laid out once per workgroup in LDS, parameter gradients through per-wavefront LDS transposes.
+// What is new against tu_trpo.hip:
+//   * the ReLU mask (h > 0) replaces 1 - h^2;
+//   * the critic's merge layer: the action joins as four more k-steps with the action a = v + 4 h in register v < 4 of lane (sample, h) --
+//     the layout in which the actor's output layer leaves mu(s), so Q(s, mu(s)) needs no data movement, and the layout of the cotangent
+//     dQ/da that the actor's reverse pass takes (tu_trpo.hip's `wt`);
+//   * the critic's output layer has one row: q is a 16-term dot product per lane plus one cross-half shuffle, its gradient a per-lane
+//     accumulation reduced over the lanes once per wavefront;
+//   * every per-sample row is gathered from the pool through the batch's index (clamped to the pool's capacity);
+//   * the four wavefronts of a workgroup add their accumulators in LDS in a fixed order: one partial row per WORKGROUP, at most 256 rows,
+//     so that the single-workgroup apply kernel reads 2 MB and not 18.
+// Every sum runs in a fixed order (k-ordered MFMA chains, tiles in a fixed order per wavefront, a fixed grid for a given n): a run repeats
+// bit for bit.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/cassie_trpo.h"
+#include "../../include/cassie_vec.h"
+
+namespace cassie_ddpg {
+
+constexpr int H = 32;
+constexpr int TP = 36;            // floats per row of a transpose tile (tu_trpo.hip)
+constexpr int WAVES = 4;
+constexpr int MAX_BLOCKS = 256;   // one workgroup per CU; one partial row per workgroup
+
+template <int D, int A> struct Shape {
+  static constexpr int HA = H + A;   // row length of the critic's merge layer
+  // actor row  [W1 | b1 | W2 | b2 | W3 | b3]
+  static constexpr int NPA = H * D + H + H * H + H + A * H + A;
+  static constexpr int A_W1 = 0, A_B1 = H * D, A_W2 = A_B1 + H, A_B2 = A_W2 + H * H, A_W3 = A_B2 + H, A_B3 = A_W3 + A * H;
+  // critic row [W1 | b1 | W2 | b2 | W3 | b3]
+  static constexpr int NPQ = H * D + H + H * HA + H + H + 1;
+  static constexpr int Q_W1 = 0, Q_B1 = H * D, Q_W2 = Q_B1 + H, Q_B2 = Q_W2 + H * HA, Q_W3 = Q_B2 + H, Q_B3 = Q_W3 + H;
+};
+
+struct Net { const float *W1, *b1, *W2, *b2, *W3, *b3; };
+struct NetRW { float *W1, *b1, *W2, *b2, *W3, *b3; };
+struct Pool { const float *obs, *act, *rew, *term, *nobs; long long cap; };
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+#define DDPG_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+
+__device__ __forceinline__ float tanh_fast(float x) {   // tu_trpo.hip: 1 - 2 / (e^2x + 1), absolute error ~1e-7
+  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
+  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
+}
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ int row_of(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
+
+// Element `st` (k-step) of the A operand of a product for lane (c, h): see tu_trpo.hip's header for why W[c][r(st, h)] is what k-step st
+// of Y = W X needs when X sits in the accumulator layout.
+enum Kind {
+  K_FIRST,   // first layer, W [32][D]: k = 2 st + h
+  K_HID,     // W [32][32] on an activation
+  K_HIDQ,    // the critic's W2 [32][32 + A], hidden columns
+  K_OUT,     // the actor's W3 [A][32] padded to 32 rows
+  K_HIDT,    // W [32][32] transposed (reverse mode)
+  K_HIDQT,   // the critic's W2 hidden columns transposed
+  K_ACTIN,   // the critic's W2 action columns: k-step st < 4 sums over action a = st + 4 h
+  K_W3T,     // the actor's W3 transposed: cotangent row a = st + 4 h, st < 4
+  K_DA       // the critic's W2 action columns transposed, padded to 32 rows: dQ/da = W2a' G2
+};
+template <int D, int A> __device__ __forceinline__ float wel(int kind, const float* __restrict__ W, int st, int c, int h) {
+  constexpr int HA = H + A, KS1 = (D + 1) / 2;
+  const int r = row_of(st, h);
+  switch (kind) {
+    case K_FIRST: { const int k = 2 * st + h; return (st < KS1 && k < D) ? W[c * D + k] : 0.0f; }
+    case K_HID: return W[c * H + r];
+    case K_HIDQ: return W[c * HA + r];
+    case K_OUT: return c < A ? W[c * H + r] : 0.0f;
+    case K_HIDT: return W[r * H + c];
+    case K_HIDQT: return W[r * HA + c];
+    case K_ACTIN: { const int a = st + 4 * h; return (st < 4 && a < A) ? W[c * HA + H + a] : 0.0f; }
+    case K_W3T: { const int a = st + 4 * h; return (st < 4 && a < A) ? W[a * H + c] : 0.0f; }
+    default: return c < A ? W[r * HA + H + c] : 0.0f;   // K_DA
+  }
+}
+struct Grp { int kind; const float* W; int q0, nq; };
+
+template <int D, int A, int NG> __device__ __forceinline__ void fill_images(float4 (*wimg)[64], const Grp (&g)[NG], int wave, int lane) {
+  const int c = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int k = 0; k < NG; k++) {
+    for (int q = wave; q < g[k].nq; q += WAVES) {
+      float v4[4];
+#pragma unroll
+      for (int e = 0; e < 4; e++) v4[e] = wel<D, A>(g[k].kind, g[k].W, 4 * q + e, c, h);
+      wimg[g[k].q0 + q][lane] = make_float4(v4[0], v4[1], v4[2], v4[3]);
+    }
+  }
+}
+__device__ __forceinline__ void aop(const float4 (*wimg)[64], int q0, int lane, float (&a)[16]) {   // the 16 k-steps of a product
+#pragma unroll
+  for (int q = 0; q < 4; q++) { const float4 w = wimg[q0 + q][lane]; a[4 * q] = w.x; a[4 * q + 1] = w.y; a[4 * q + 2] = w.z; a[4 * q + 3] = w.w; }
+}
+__device__ __forceinline__ v16f bias_tile(const float* sb, int h) {   // C operand: bias[r(v, h)] in register v
+  v16f z;
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    const float4 b = *reinterpret_cast<const float4*>(&sb[8 * g + 4 * h]);
+    z[4 * g] = b.x; z[4 * g + 1] = b.y; z[4 * g + 2] = b.z; z[4 * g + 3] = b.w;
+  }
+  return z;
+}
+__device__ __forceinline__ void put(float* t, const v16f& x, int c, int h) {   // accumulator layout -> [row][sample] image
+#pragma unroll
+  for (int v = 0; v < 16; v++) t[row_of(v, h) * TP + c] = x[v];
+}
+__device__ __forceinline__ void get(const float* t, float (&y)[16], int c, int h) {   // lane (i = c, h): row i, samples 16 h .. 16 h + 15
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const float4 b = *reinterpret_cast<const float4*>(&t[c * TP + 16 * h + 4 * q]);
+    y[4 * q] = b.x; y[4 * q + 1] = b.y; y[4 * q + 2] = b.z; y[4 * q + 3] = b.w;
+  }
+}
+__device__ __forceinline__ void relu16(v16f& x) {
+#pragma unroll
+  for (int v = 0; v < 16; v++) x[v] = x[v] > 0.0f ? x[v] : 0.0f;
+}
+__device__ __forceinline__ long long clamp_row(long long i, long long cap) { return i < 0 ? 0 : (i >= cap ? cap - 1 : i); }
+
+// hidden layers of a network on the first-layer operand xb: h1 = relu(W1 x + b1) and z2 = W2 h1 + b2 (not yet rectified: the critic adds
+// its action columns first)
+template <int KS1> __device__ __forceinline__ void two_layers(const float4 (*wimg)[64], int qW1, int qW2, const float* sb1, const float* sb2, const float (&xb)[KS1],
+                                                              int lane, int h, v16f& h1, v16f& z2) {
+  float aw[16];
+  h1 = bias_tile(sb1, h);
+  aop(wimg, qW1, lane, aw);
+#pragma unroll
+  for (int s = 0; s < KS1; s++) h1 = DDPG_MFMA(aw[s], xb[s], h1);
+  relu16(h1);
+  z2 = bias_tile(sb2, h);
+  aop(wimg, qW2, lane, aw);
+#pragma unroll
+  for (int v = 0; v < 16; v++) z2 = DDPG_MFMA(aw[v], h1[v], z2);
+}
+// + W2[:, 32:] a for the action a = v + 4 h in register v < 4 (one quad of k-steps)
+__device__ __forceinline__ void add_action(const float4 (*wimg)[64], int qA, int lane, const float (&ab)[4], v16f& z2) {
+  const float4 w = wimg[qA][lane];
+  z2 = DDPG_MFMA(w.x, ab[0], z2); z2 = DDPG_MFMA(w.y, ab[1], z2); z2 = DDPG_MFMA(w.z, ab[2], z2); z2 = DDPG_MFMA(w.w, ab[3], z2);
+}
+// q = b3 + W3 . h2 for the sample of this lane (both halves of the wavefront hold the result)
+__device__ __forceinline__ float q_head(const float (&w3)[16], float b3, const v16f& h2) {
+  float q = 0.0f;
+#pragma unroll
+  for (int v = 0; v < 16; v++) q = __builtin_fmaf(w3[v], h2[v], q);
+  q += __shfl_xor(q, 32, 64);
+  return q + b3;
+}
+
+// the wavefronts' rows of partial sums -> one row per workgroup, added in the order wave 0, 1, 2, 3
+template <int NROW> __device__ __forceinline__ void reduce_rows(const float* red, float* __restrict__ out) {
+  for (int i = threadIdx.x; i < NROW; i += 64 * WAVES) out[i] = ((red[i] + red[NROW + i]) + red[2 * NROW + i]) + red[3 * NROW + i];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- critic gradient
+// Per sample b of the batch (pool row i = idx[b]):  y = r_i + (1 - terminal_i) gamma Q'(s'_i, mu'(s'_i)),  e = Q(s_i, a_i) - y, and the
+// gradient of sum_b e^2 with respect to the live critic.  Row: [gW1 | gb1 | gW2 | gb2 | gW3 | gb3 | sum e^2 | sum Q].
+enum { CQ_TA_W1 = 0, CQ_TA_W2 = 4, CQ_TA_W3 = 8, CQ_TQ_W1 = 12, CQ_TQ_W2 = 16, CQ_TQ_A = 20, CQ_Q_W1 = 21, CQ_Q_W2 = 25, CQ_Q_A = 29, CQ_Q_W2T = 30, CQ_N = 34 };
+template <int D, int A>
+__global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, const long long* __restrict__ idx, int n, Net ta, Net tq, Net q, float gamma,
+                                                                    float* __restrict__ partial) {
+  typedef Shape<D, A> S;
+  static_assert(D < 32 && A <= 8, "a column of ones next to the observations; the action rows in registers 0..3 of the two lane halves");
+  constexpr int KS1 = (D + 1) / 2, NROW = S::NPQ + 2;
+  static_assert(WAVES * NROW <= WAVES * 2 * 32 * TP, "the workgroup's reduction re-uses the transpose tiles");
+  __shared__ alignas(16) float tilemem[WAVES * 2 * 32 * TP];
+  __shared__ alignas(16) float sbias[7][32];   // target actor b1 b2 b3, target critic b1 b2, live critic b1 b2
+  __shared__ float4 wimg[CQ_N][64];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, h = lane >> 5;
+  if (tid < 32) {
+    sbias[0][tid] = ta.b1[tid]; sbias[1][tid] = ta.b2[tid]; sbias[2][tid] = tid < A ? ta.b3[tid] : 0.0f;
+    sbias[3][tid] = tq.b1[tid]; sbias[4][tid] = tq.b2[tid]; sbias[5][tid] = q.b1[tid]; sbias[6][tid] = q.b2[tid];
+  }
+  {
+    const Grp g[10] = {{K_FIRST, ta.W1, CQ_TA_W1, 4}, {K_HID, ta.W2, CQ_TA_W2, 4}, {K_OUT, ta.W3, CQ_TA_W3, 4}, {K_FIRST, tq.W1, CQ_TQ_W1, 4},
+                       {K_HIDQ, tq.W2, CQ_TQ_W2, 4}, {K_ACTIN, tq.W2, CQ_TQ_A, 1}, {K_FIRST, q.W1, CQ_Q_W1, 4}, {K_HIDQ, q.W2, CQ_Q_W2, 4},
+                       {K_ACTIN, q.W2, CQ_Q_A, 1}, {K_HIDQT, q.W2, CQ_Q_W2T, 4}};
+    fill_images<D, A>(wimg, g, wave, lane);
+  }
+  float w3t[16], w3q[16];
+#pragma unroll
+  for (int v = 0; v < 16; v++) { w3t[v] = tq.W3[row_of(v, h)]; w3q[v] = q.W3[row_of(v, h)]; }
+  const float b3t = tq.b3[0], b3q = q.b3[0];
+  __syncthreads();
+  float* t0 = tilemem + (wave * 2) * 32 * TP;
+  float* t1 = t0 + 32 * TP;
+  v16f gW1, gW2, gW2a;
+  float gW3[16];
+#pragma unroll
+  for (int v = 0; v < 16; v++) { gW1[v] = 0.0f; gW2[v] = 0.0f; gW2a[v] = 0.0f; gW3[v] = 0.0f; }
+  float gb2 = 0.0f, gb3 = 0.0f, sse = 0.0f, sq = 0.0f;
+  const int ntiles = (n + 31) / 32;
+  for (int tl = blockIdx.x * WAVES + wave; tl < ntiles; tl += gridDim.x * WAVES) {
+    const int s0 = tl * 32, smp = s0 + c;
+    const bool valid = smp < n;
+    const long long gi = valid ? clamp_row(idx[smp], pool.cap) : 0;
+    float xb[KS1], xn[KS1], ab[4], xt[16], at[16];
+#pragma unroll
+    for (int s = 0; s < KS1; s++) {
+      const int k = 2 * s + h;
+      const bool on = valid && k < D;
+      xb[s] = on ? pool.obs[gi * D + k] : 0.0f; xn[s] = on ? pool.nobs[gi * D + k] : 0.0f;
+    }
+#pragma unroll
+    for (int v = 0; v < 4; v++) ab[v] = (valid && v + 4 * h < A) ? pool.act[gi * A + v + 4 * h] : 0.0f;
+    // transposed operands of the parameter gradients: feature (action component) on the lane, column D (A) = ones
+#pragma unroll
+    for (int s = 0; s < 16; s++) {
+      const int sm = s0 + 16 * h + s;
+      const bool on = sm < n;
+      const long long gs = on ? clamp_row(idx[sm], pool.cap) : 0;
+      xt[s] = c < D ? (on ? pool.obs[gs * D + c] : 0.0f) : (c == D ? 1.0f : 0.0f);
+      at[s] = (c < A && on) ? pool.act[gs * A + c] : 0.0f;
+    }
+    const float rew = valid ? pool.rew[gi] : 0.0f, live = valid ? 1.0f - pool.term[gi] : 0.0f;
+    // ---- target: Q'(s', mu'(s'))
+    v16f u1, u2;
+    float mt[4];
+    {
+      v16f a1, a2;
+      two_layers<KS1>(wimg, CQ_TA_W1, CQ_TA_W2, sbias[0], sbias[1], xn, lane, h, a1, a2);
+      relu16(a2);
+      float aw[16];
+      v16f mu = bias_tile(sbias[2], h);
+      aop(wimg, CQ_TA_W3, lane, aw);
+#pragma unroll
+      for (int v = 0; v < 16; v++) mu = DDPG_MFMA(aw[v], a2[v], mu);
+#pragma unroll
+      for (int v = 0; v < 4; v++) mt[v] = tanh_fast(mu[v]);   // rows a >= A: W3 and b3 padded with zeros -> tanh(0) = 0
+    }
+    two_layers<KS1>(wimg, CQ_TQ_W1, CQ_TQ_W2, sbias[3], sbias[4], xn, lane, h, u1, u2);
+    add_action(wimg, CQ_TQ_A, lane, mt, u2);
+    relu16(u2);
+    const float y = rew + live * gamma * q_head(w3t, b3t, u2);
+    // ---- live critic at (s, a)
+    v16f c1, c2;
+    two_layers<KS1>(wimg, CQ_Q_W1, CQ_Q_W2, sbias[5], sbias[6], xb, lane, h, c1, c2);
+    add_action(wimg, CQ_Q_A, lane, ab, c2);
+    relu16(c2);
+    const float qv = q_head(w3q, b3q, c2);
+    const float e = valid ? qv - y : 0.0f, dq = 2.0f * e;
+    if (h == 0 && valid) { sse += e * e; sq += qv; gb3 += dq; }
+    // ---- reverse mode: G2 = (W3' dq) o (h2 > 0), G1 = (W2h' G2) o (h1 > 0)
+    v16f g2, g1;
+#pragma unroll
+    for (int v = 0; v < 16; v++) {
+      gW3[v] = __builtin_fmaf(dq, c2[v], gW3[v]);
+      g2[v] = c2[v] > 0.0f ? w3q[v] * dq : 0.0f;
+      g1[v] = 0.0f;
+    }
+    float aw[16], ta_[16], tb_[16];
+    aop(wimg, CQ_Q_W2T, lane, aw);
+#pragma unroll
+    for (int v = 0; v < 16; v++) g1 = DDPG_MFMA(aw[v], g2[v], g1);
+#pragma unroll
+    for (int v = 0; v < 16; v++) g1[v] = c1[v] > 0.0f ? g1[v] : 0.0f;
+    put(t0, g2, c, h); put(t1, c1, c, h);
+    wave_lds_sync();
+    get(t0, ta_, c, h); get(t1, tb_, c, h);
+    wave_lds_sync();
+#pragma unroll
+    for (int s = 0; s < 16; s++) { gW2 = DDPG_MFMA(ta_[s], tb_[s], gW2); gW2a = DDPG_MFMA(ta_[s], at[s], gW2a); gb2 += ta_[s]; }
+    put(t0, g1, c, h);
+    wave_lds_sync();
+    get(t0, ta_, c, h);
+    wave_lds_sync();
+#pragma unroll
+    for (int s = 0; s < 16; s++) gW1 = DDPG_MFMA(ta_[s], xt[s], gW1);
+  }
+  // ---- this wavefront's row in LDS (the tiles are free once every wavefront has left the loop), then one row per workgroup
+#pragma unroll
+  for (int v = 0; v < 16; v++) {
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) gW3[v] += __shfl_xor(gW3[v], m, 64);   // over the 32 samples of the lane half
+  }
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) { sse += __shfl_xor(sse, m, 64); sq += __shfl_xor(sq, m, 64); gb3 += __shfl_xor(gb3, m, 64); }
+  gb2 += __shfl_xor(gb2, 32, 64);
+  __syncthreads();
+  float* red = tilemem + wave * NROW;
+#pragma unroll
+  for (int v = 0; v < 16; v++) {
+    const int r = row_of(v, h);
+    red[S::Q_W2 + r * S::HA + c] = gW2[v];
+    if (c < A) red[S::Q_W2 + r * S::HA + H + c] = gW2a[v];
+    if (c < D) red[S::Q_W1 + r * D + c] = gW1[v];
+    if (c == D) red[S::Q_B1 + r] = gW1[v];
+    if (c == 0) red[S::Q_W3 + r] = gW3[v];
+  }
+  if (h == 0) red[S::Q_B2 + c] = gb2;
+  if (lane == 0) { red[S::Q_B3] = gb3; red[S::NPQ] = sse; red[S::NPQ + 1] = sq; }
+  __syncthreads();
+  reduce_rows<NROW>(tilemem, partial + (size_t)blockIdx.x * NROW);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- actor gradient
+// Gradient of -sum_b Q(s_b, mu(s_b)) with respect to the actor, through the live critic.  Row: [gW1 | gb1 | gW2 | gb2 | gW3 | gb3 | sum Q].
+enum { AG_W1 = 0, AG_W2 = 4, AG_W3 = 8, AG_W2T = 12, AG_W3T = 16, AG_Q_W1 = 17, AG_Q_W2 = 21, AG_Q_A = 25, AG_Q_DA = 26, AG_N = 30 };
+template <int D, int A>
+__global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, const long long* __restrict__ idx, int n, Net th, Net q, float* __restrict__ partial) {
+  typedef Shape<D, A> S;
+  static_assert(D < 32 && A <= 8, "see critic_grad_kernel");
+  constexpr int KS1 = (D + 1) / 2, NROW = S::NPA + 1;
+  static_assert(WAVES * NROW <= WAVES * 2 * 32 * TP, "the workgroup's reduction re-uses the transpose tiles");
+  __shared__ alignas(16) float tilemem[WAVES * 2 * 32 * TP];
+  __shared__ alignas(16) float sbias[5][32];   // actor b1 b2 b3, critic b1 b2
+  __shared__ float4 wimg[AG_N][64];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, h = lane >> 5;
+  if (tid < 32) {
+    sbias[0][tid] = th.b1[tid]; sbias[1][tid] = th.b2[tid]; sbias[2][tid] = tid < A ? th.b3[tid] : 0.0f;
+    sbias[3][tid] = q.b1[tid]; sbias[4][tid] = q.b2[tid];
+  }
+  {
+    const Grp g[9] = {{K_FIRST, th.W1, AG_W1, 4}, {K_HID, th.W2, AG_W2, 4}, {K_OUT, th.W3, AG_W3, 4}, {K_HIDT, th.W2, AG_W2T, 4}, {K_W3T, th.W3, AG_W3T, 1},
+                      {K_FIRST, q.W1, AG_Q_W1, 4}, {K_HIDQ, q.W2, AG_Q_W2, 4}, {K_ACTIN, q.W2, AG_Q_A, 1}, {K_DA, q.W2, AG_Q_DA, 4}};
+    fill_images<D, A>(wimg, g, wave, lane);
+  }
+  float w3q[16];
+#pragma unroll
+  for (int v = 0; v < 16; v++) w3q[v] = q.W3[row_of(v, h)];
+  const float b3q = q.b3[0];
+  __syncthreads();
+  float* t0 = tilemem + (wave * 2) * 32 * TP;
+  float* t1 = t0 + 32 * TP;
+  v16f gW1, gW2, gW3;
+#pragma unroll
+  for (int v = 0; v < 16; v++) { gW1[v] = 0.0f; gW2[v] = 0.0f; gW3[v] = 0.0f; }
+  float gb2 = 0.0f, gb3 = 0.0f, sq = 0.0f;
+  const int ntiles = (n + 31) / 32;
+  for (int tl = blockIdx.x * WAVES + wave; tl < ntiles; tl += gridDim.x * WAVES) {
+    const int s0 = tl * 32, smp = s0 + c;
+    const bool valid = smp < n;
+    const long long gi = valid ? clamp_row(idx[smp], pool.cap) : 0;
+    float xb[KS1], xt[16];
+#pragma unroll
+    for (int s = 0; s < KS1; s++) { const int k = 2 * s + h; xb[s] = (valid && k < D) ? pool.obs[gi * D + k] : 0.0f; }
+#pragma unroll
+    for (int s = 0; s < 16; s++) {
+      const int sm = s0 + 16 * h + s;
+      const bool on = sm < n;
+      const long long gs = on ? clamp_row(idx[sm], pool.cap) : 0;
+      xt[s] = c < D ? (on ? pool.obs[gs * D + c] : 0.0f) : (c == D ? 1.0f : 0.0f);
+    }
+    // ---- actor forward: mu(s), action a = v + 4 h in register v < 4
+    v16f a1, a2;
+    float aw[16], mu[4];
+    two_layers<KS1>(wimg, AG_W1, AG_W2, sbias[0], sbias[1], xb, lane, h, a1, a2);
+    relu16(a2);
+    {
+      v16f z3 = bias_tile(sbias[2], h);
+      aop(wimg, AG_W3, lane, aw);
+#pragma unroll
+      for (int v = 0; v < 16; v++) z3 = DDPG_MFMA(aw[v], a2[v], z3);
+#pragma unroll
+      for (int v = 0; v < 4; v++) mu[v] = tanh_fast(z3[v]);
+    }
+    // ---- critic at (s, mu(s)) and dQ/da = W2a' (W3 o (h2 > 0))
+    v16f c1, c2, da;
+    two_layers<KS1>(wimg, AG_Q_W1, AG_Q_W2, sbias[3], sbias[4], xb, lane, h, c1, c2);
+    add_action(wimg, AG_Q_A, lane, mu, c2);
+    relu16(c2);
+    const float qv = q_head(w3q, b3q, c2);
+    if (h == 0 && valid) sq += qv;
+#pragma unroll
+    for (int v = 0; v < 16; v++) da[v] = 0.0f;
+    aop(wimg, AG_Q_DA, lane, aw);
+#pragma unroll
+    for (int v = 0; v < 16; v++) da = DDPG_MFMA(aw[v], c2[v] > 0.0f ? w3q[v] : 0.0f, da);
+    // cotangent of -Q on the output layer's pre-activation
+    v16f wt;
+#pragma unroll
+    for (int v = 0; v < 16; v++) wt[v] = 0.0f;
+#pragma unroll
+    for (int v = 0; v < 4; v++) wt[v] = (valid && v + 4 * h < A) ? -da[v] * (1.0f - mu[v] * mu[v]) : 0.0f;
+    // ---- the actor's reverse pass (tu_trpo.hip with the ReLU mask)
+    v16f g2, g1;
+#pragma unroll
+    for (int v = 0; v < 16; v++) { g2[v] = 0.0f; g1[v] = 0.0f; }
+    {
+      const float4 w = wimg[AG_W3T][lane];
+      g2 = DDPG_MFMA(w.x, wt[0], g2); g2 = DDPG_MFMA(w.y, wt[1], g2); g2 = DDPG_MFMA(w.z, wt[2], g2); g2 = DDPG_MFMA(w.w, wt[3], g2);
+    }
+#pragma unroll
+    for (int v = 0; v < 16; v++) g2[v] = a2[v] > 0.0f ? g2[v] : 0.0f;
+    aop(wimg, AG_W2T, lane, aw);
+#pragma unroll
+    for (int v = 0; v < 16; v++) g1 = DDPG_MFMA(aw[v], g2[v], g1);
+#pragma unroll
+    for (int v = 0; v < 16; v++) g1[v] = a1[v] > 0.0f ? g1[v] : 0.0f;
+    float ta_[16], tb_[16];
+    put(t0, g2, c, h); put(t1, a1, c, h);
+    wave_lds_sync();
+    get(t0, ta_, c, h); get(t1, tb_, c, h);
+    wave_lds_sync();
+#pragma unroll
+    for (int s = 0; s < 16; s++) { gW2 = DDPG_MFMA(ta_[s], tb_[s], gW2); gb2 += ta_[s]; }
+    put(t0, g1, c, h);
+    wave_lds_sync();
+    get(t0, ta_, c, h);
+    wave_lds_sync();
+#pragma unroll
+    for (int s = 0; s < 16; s++) gW1 = DDPG_MFMA(ta_[s], xt[s], gW1);
+    put(t0, wt, c, h); put(t1, a2, c, h);
+    wave_lds_sync();
+    get(t0, ta_, c, h); get(t1, tb_, c, h);
+    wave_lds_sync();
+#pragma unroll
+    for (int s = 0; s < 16; s++) { gW3 = DDPG_MFMA(ta_[s], tb_[s], gW3); gb3 += ta_[s]; }
+  }
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) sq += __shfl_xor(sq, m, 64);
+  gb2 += __shfl_xor(gb2, 32, 64); gb3 += __shfl_xor(gb3, 32, 64);
+  __syncthreads();
+  float* red = tilemem + wave * NROW;
+#pragma unroll
+  for (int v = 0; v < 16; v++) {
+    const int r = row_of(v, h);
+    red[S::A_W2 + r * H + c] = gW2[v];
+    if (c < D) red[S::A_W1 + r * D + c] = gW1[v];
+    if (c == D) red[S::A_B1 + r] = gW1[v];
+    if (r < A) red[S::A_W3 + r * H + c] = gW3[v];
+  }
+  if (h == 0) red[S::A_B2 + c] = gb2;
+  if (h == 0 && c < A) red[S::A_B3 + c] = gb3;
+  if (lane == 0) red[S::NPA] = sq;
+  __syncthreads();
+  reduce_rows<NROW>(tilemem, partial + (size_t)blockIdx.x * NROW);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- apply
+// g = scale * (rows of partial added in order);  Lasagne's Adam on the live network (tu_pg.hip: pg_adam_kernel);  target <- (1 - tau) target
+// + tau live;  stats[k] += the row sums of the `ns` columns behind the gradient (float64).  One workgroup.
+struct Offsets { int o[7]; };   // starts of W1, b1, W2, b2, W3, b3 in the row, and the parameter count
+__global__ void __launch_bounds__(1024) apply_kernel(int rows, int ns, const float* __restrict__ partial, float scale, NetRW live, NetRW targ, Offsets off,
+                                                     float* __restrict__ m, float* __restrict__ v, float a, float beta1, float beta2, float eps, float tau,
+                                                     double* __restrict__ stats) {
+  const int np = off.o[6], stride = np + ns;
+  for (int i = threadIdx.x; i < np; i += 1024) {
+    float g = 0.0f;
+    const float* p = partial + i;
+    int r = 0;
+    for (; r + 8 <= rows; r += 8) {   // eight loads in flight, added in row order
+      float x[8];
+#pragma unroll
+      for (int k = 0; k < 8; k++) x[k] = p[(size_t)(r + k) * stride];
+#pragma unroll
+      for (int k = 0; k < 8; k++) g += x[k];
+    }
+    for (; r < rows; r++) g += p[(size_t)r * stride];
+    g *= scale;
+    float *th, *tg;
+    int j;
+    if (i < off.o[1]) { th = live.W1; tg = targ.W1; j = i - off.o[0]; }
+    else if (i < off.o[2]) { th = live.b1; tg = targ.b1; j = i - off.o[1]; }
+    else if (i < off.o[3]) { th = live.W2; tg = targ.W2; j = i - off.o[2]; }
+    else if (i < off.o[4]) { th = live.b2; tg = targ.b2; j = i - off.o[3]; }
+    else if (i < off.o[5]) { th = live.W3; tg = targ.W3; j = i - off.o[4]; }
+    else { th = live.b3; tg = targ.b3; j = i - off.o[5]; }
+    const float mi = beta1 * m[i] + (1.0f - beta1) * g;
+    const float vi = beta2 * v[i] + (1.0f - beta2) * (g * g);
+    m[i] = mi; v[i] = vi;
+    const float t = th[j] - a * mi / (sqrtf(vi) + eps);
+    th[j] = t;
+    tg[j] = (1.0f - tau) * tg[j] + tau * t;
+  }
+  if ((int)threadIdx.x < ns && stats) {
+    double s = 0.0;
+    for (int r = 0; r < rows; r++) s += (double)partial[(size_t)r * stride + np + threadIdx.x];
+    stats[threadIdx.x] += s;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- policy step
+// tu_trpo.hip's policy_step_mfma_kernel with ReLU hidden units, a tanh output and Ornstein-Uhlenbeck noise (rllab's OUStrategy):
+//   x = path_t == 0 ? mu : ou;  x += theta (mu - x) + sigma noise;  act = clip(mu(s) + x, -1, 1)
+// obs32 and act are the pool's rows [top, top + n) (the caller passes the offset pointers).
+template <int D, int A>
+__global__ void __launch_bounds__(64 * WAVES, 2) policy_step_kernel(const double* __restrict__ obs, int n, Net th, const float* __restrict__ noise,
+                                                                    const long long* __restrict__ path_t, float ou_theta, float ou_sigma, float ou_mu,
+                                                                    float* __restrict__ ou, const double* __restrict__ low, const double* __restrict__ high,
+                                                                    float* __restrict__ obs32, float* __restrict__ act, double* __restrict__ env_act) {
+  constexpr int KS1 = (D + 1) / 2;
+  __shared__ alignas(16) float sbias[3][32];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, h = lane >> 5;
+  if (tid < 32) { sbias[0][tid] = th.b1[tid]; sbias[1][tid] = th.b2[tid]; sbias[2][tid] = tid < A ? th.b3[tid] : 0.0f; }
+  float aW1[KS1], aW2[16], aW3[16];
+  double lo[4], hi[4];
+#pragma unroll
+  for (int s = 0; s < KS1; s++) aW1[s] = wel<D, A>(K_FIRST, th.W1, s, c, h);
+#pragma unroll
+  for (int v = 0; v < 16; v++) { aW2[v] = wel<D, A>(K_HID, th.W2, v, c, h); aW3[v] = wel<D, A>(K_OUT, th.W3, v, c, h); }
+#pragma unroll
+  for (int v = 0; v < 4; v++) { const int a = v + 4 * h; lo[v] = a < A ? low[a] : 0.0; hi[v] = a < A ? high[a] : 0.0; }
+  __syncthreads();
+  const int tl = blockIdx.x * WAVES + wave;   // one tile per wavefront
+  const int smp = tl * 32 + c;
+  const bool valid = smp < n;
+  float xb[KS1];
+#pragma unroll
+  for (int s = 0; s < KS1; s++) {
+    const int k = 2 * s + h;
+    const bool on = valid && k < D;
+    xb[s] = on ? (float)obs[(size_t)smp * D + k] : 0.0f;
+    if (on) obs32[(size_t)smp * D + k] = xb[s];
+  }
+  v16f h1 = bias_tile(sbias[0], h);
+#pragma unroll
+  for (int s = 0; s < KS1; s++) h1 = DDPG_MFMA(aW1[s], xb[s], h1);
+  relu16(h1);
+  v16f h2 = bias_tile(sbias[1], h);
+#pragma unroll
+  for (int v = 0; v < 16; v++) h2 = DDPG_MFMA(aW2[v], h1[v], h2);
+  relu16(h2);
+  v16f z3 = bias_tile(sbias[2], h);
+#pragma unroll
+  for (int v = 0; v < 16; v++) z3 = DDPG_MFMA(aW3[v], h2[v], z3);
+  const bool fresh = valid && path_t[smp] == 0;
+#pragma unroll
+  for (int v = 0; v < 4; v++) {
+    const int a = v + 4 * h;
+    if (valid && a < A) {
+      const size_t o = (size_t)smp * A + a;
+      float x = fresh ? ou_mu : ou[o];
+      x = x + ou_theta * (ou_mu - x) + ou_sigma * noise[o];
+      ou[o] = x;
+      float val = tanh_fast(z3[v]) + x;
+      val = val < -1.0f ? -1.0f : (val > 1.0f ? 1.0f : val);
+      act[o] = val;
+      double e = lo[v] + ((double)val + 1.0) * 0.5 * (hi[v] - lo[v]);
+      e = e < lo[v] ? lo[v] : (e > hi[v] ? hi[v] : e);
+      env_act[o] = e;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- pool commit
+// After Env.step: reward (scaled in float64, stored in float32), terminal flag and the float32 next observation into the rows the policy
+// step opened.  One lane per element of the next observation; the lane of element 0 also writes the two scalars of its row.
+__global__ void __launch_bounds__(256) pool_commit_kernel(const double* __restrict__ rew, const uint8_t* __restrict__ done, const double* __restrict__ nobs, int n,
+                                                          int D, double scale, float* __restrict__ prew, float* __restrict__ pterm, float* __restrict__ pnobs) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)n * D) return;
+  pnobs[e] = (float)nobs[e];
+  if (e % D == 0) {
+    const size_t i = e / D;
+    prew[i] = (float)(scale * rew[i]);
+    pterm[i] = done[i] != 0 ? 1.0f : 0.0f;
+  }
+}
+
+inline int blocks_for(int n) {
+  const int tiles = (n + 31) / 32;
+  const int b = (tiles + WAVES - 1) / WAVES;
+  return b < 1 ? 1 : (b > MAX_BLOCKS ? MAX_BLOCKS : b);
+}
+inline bool shape_ok(int D, int A) { return (D == 26 || D == 17) && (A == 6 || A == 7); }
+inline bool net_ok(const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3) { return W1 && b1 && W2 && b2 && W3 && b3; }
+inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+inline bool pool_ok(const Pool& p) { return p.obs && p.act && p.rew && p.term && p.nobs && p.cap > 0; }
+
+}  // namespace cassie_ddpg
+
+extern "C" {
+
+int CassieDdpgParamCount(int obs_dim, int act_dim, int which) {
+  if (!cassie_ddpg::shape_ok(obs_dim, act_dim)) return 0;
+  if (which == CASSIE_DDPG_ACTOR) return 32 * obs_dim + 32 + 32 * 32 + 32 + act_dim * 32 + act_dim;
+  if (which == CASSIE_DDPG_CRITIC) return 32 * obs_dim + 32 + 32 * (32 + act_dim) + 32 + 32 + 1;
+  return 0;
+}
+int CassieDdpgPartialRows(int batch) { return batch > 0 ? cassie_ddpg::blocks_for(batch) : 0; }
+
+int CassieDdpgPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                         const float* b3, const float* noise_dev, const long long* path_t_dev, float ou_theta, float ou_sigma, float ou_mu, float* ou_state_dev,
+                         const double* low_dev, const double* high_dev, float* pool_obs_row_dev, float* pool_act_row_dev, double* env_actions_dev, void* stream) {
+  using namespace cassie_ddpg;
+  if (!obs_dev || n <= 0 || !net_ok(W1, b1, W2, b2, W3, b3) || !noise_dev || !path_t_dev || !ou_state_dev || !low_dev || !high_dev || !pool_obs_row_dev ||
+      !pool_act_row_dev || !env_actions_dev)
+    return CASSIE_EINVAL;
+  const Net th{W1, b1, W2, b2, W3, b3};
+  const dim3 grid(((n + 31) / 32 + WAVES - 1) / WAVES), block(64 * WAVES);
+  hipStream_t s = (hipStream_t)stream;
+#define DDPG_STEP(D_, A_) hipLaunchKernelGGL((policy_step_kernel<D_, A_>), grid, block, 0, s, obs_dev, n, th, noise_dev, path_t_dev, ou_theta, ou_sigma, ou_mu, \
+                                             ou_state_dev, low_dev, high_dev, pool_obs_row_dev, pool_act_row_dev, env_actions_dev)
+  if (obs_dim == 26 && act_dim == 6) DDPG_STEP(26, 6);
+  else if (obs_dim == 26 && act_dim == 7) DDPG_STEP(26, 7);
+  else return CASSIE_EINVAL;
+#undef DDPG_STEP
+  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+}
+
+int CassieDdpgPoolCommit(const double* rew_dev, const unsigned char* done_dev, const double* next_obs_dev, int n, int obs_dim, double scale_reward,
+                         float* pool_rew_row_dev, float* pool_term_row_dev, float* pool_next_obs_row_dev, void* stream) {
+  if (!rew_dev || !done_dev || !next_obs_dev || n <= 0 || obs_dim <= 0 || !pool_rew_row_dev || !pool_term_row_dev || !pool_next_obs_row_dev) return CASSIE_EINVAL;
+  const size_t total = (size_t)n * obs_dim;
+  hipLaunchKernelGGL(cassie_ddpg::pool_commit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rew_dev, done_dev, next_obs_dev, n,
+                     obs_dim, scale_reward, pool_rew_row_dev, pool_term_row_dev, pool_next_obs_row_dev);
+  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+}
+
+int CassieDdpgCriticGrad(const float* pool_obs, const float* pool_act, const float* pool_rew, const float* pool_term, const float* pool_next_obs,
+                         long long pool_capacity, const long long* idx_dev, int batch, int obs_dim, int act_dim,
+                         const float* const* target_actor, const float* const* target_critic, const float* const* critic, float discount, float* partial_dev,
+                         void* stream) {
+  using namespace cassie_ddpg;
+  const Pool pool{pool_obs, pool_act, pool_rew, pool_term, pool_next_obs, pool_capacity};
+  if (!pool_ok(pool) || !idx_dev || batch <= 0 || !target_actor || !target_critic || !critic || !partial_dev || !aligned4(partial_dev)) return CASSIE_EINVAL;
+  const Net ta{target_actor[0], target_actor[1], target_actor[2], target_actor[3], target_actor[4], target_actor[5]};
+  const Net tq{target_critic[0], target_critic[1], target_critic[2], target_critic[3], target_critic[4], target_critic[5]};
+  const Net q{critic[0], critic[1], critic[2], critic[3], critic[4], critic[5]};
+  if (!net_ok(ta.W1, ta.b1, ta.W2, ta.b2, ta.W3, ta.b3) || !net_ok(tq.W1, tq.b1, tq.W2, tq.b2, tq.W3, tq.b3) || !net_ok(q.W1, q.b1, q.W2, q.b2, q.W3, q.b3))
+    return CASSIE_EINVAL;
+  const dim3 grid(blocks_for(batch)), block(64 * WAVES);
+  hipStream_t s = (hipStream_t)stream;
+#define DDPG_CQ(D_, A_) hipLaunchKernelGGL((critic_grad_kernel<D_, A_>), grid, block, 0, s, pool, idx_dev, batch, ta, tq, q, discount, partial_dev)
+  if (obs_dim == 26 && act_dim == 6) DDPG_CQ(26, 6);
+  else if (obs_dim == 26 && act_dim == 7) DDPG_CQ(26, 7);
+  else if (obs_dim == 17 && act_dim == 6) DDPG_CQ(17, 6);
+  else if (obs_dim == 17 && act_dim == 7) DDPG_CQ(17, 7);
+  else return CASSIE_EINVAL;
+#undef DDPG_CQ
+  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+}
+
+int CassieDdpgActorGrad(const float* pool_obs, long long pool_capacity, const long long* idx_dev, int batch, int obs_dim, int act_dim, const float* const* actor,
+                        const float* const* critic, float* partial_dev, void* stream) {
+  using namespace cassie_ddpg;
+  if (!pool_obs || pool_capacity <= 0 || !idx_dev || batch <= 0 || !actor || !critic || !partial_dev || !aligned4(partial_dev)) return CASSIE_EINVAL;
+  const Pool pool{pool_obs, nullptr, nullptr, nullptr, nullptr, pool_capacity};
+  const Net th{actor[0], actor[1], actor[2], actor[3], actor[4], actor[5]};
+  const Net q{critic[0], critic[1], critic[2], critic[3], critic[4], critic[5]};
+  if (!net_ok(th.W1, th.b1, th.W2, th.b2, th.W3, th.b3) || !net_ok(q.W1, q.b1, q.W2, q.b2, q.W3, q.b3)) return CASSIE_EINVAL;
+  const dim3 grid(blocks_for(batch)), block(64 * WAVES);
+  hipStream_t s = (hipStream_t)stream;
+#define DDPG_AG(D_, A_) hipLaunchKernelGGL((actor_grad_kernel<D_, A_>), grid, block, 0, s, pool, idx_dev, batch, th, q, partial_dev)
+  if (obs_dim == 26 && act_dim == 6) DDPG_AG(26, 6);
+  else if (obs_dim == 26 && act_dim == 7) DDPG_AG(26, 7);
+  else if (obs_dim == 17 && act_dim == 6) DDPG_AG(17, 6);
+  else if (obs_dim == 17 && act_dim == 7) DDPG_AG(17, 7);
+  else return CASSIE_EINVAL;
+#undef DDPG_AG
+  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+}
+
+int CassieDdpgApply(int rows, int obs_dim, int act_dim, int which, const float* partial_dev, float scale, float* const* live, float* const* target, float* m_dev,
+                    float* v_dev, int t, float lr, float beta1, float beta2, float eps, float tau, double* stats_dev, void* stream) {
+  using namespace cassie_ddpg;
+  const int np = CassieDdpgParamCount(obs_dim, act_dim, which);
+  if (np == 0 || rows <= 0 || !partial_dev || !live || !target || !m_dev || !v_dev || t < 1) return CASSIE_EINVAL;
+  const NetRW lv{live[0], live[1], live[2], live[3], live[4], live[5]}, tg{target[0], target[1], target[2], target[3], target[4], target[5]};
+  if (!net_ok(lv.W1, lv.b1, lv.W2, lv.b2, lv.W3, lv.b3) || !net_ok(tg.W1, tg.b1, tg.W2, tg.b2, tg.W3, tg.b3)) return CASSIE_EINVAL;
+  const int Hh = 32, w2 = which == CASSIE_DDPG_ACTOR ? Hh * Hh : Hh * (Hh + act_dim), w3 = which == CASSIE_DDPG_ACTOR ? act_dim * Hh : Hh;
+  Offsets off;
+  off.o[0] = 0; off.o[1] = Hh * obs_dim; off.o[2] = off.o[1] + Hh; off.o[3] = off.o[2] + w2; off.o[4] = off.o[3] + Hh; off.o[5] = off.o[4] + w3; off.o[6] = np;
+  const int ns = which == CASSIE_DDPG_ACTOR ? 1 : 2;
+  const double a = (double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t));
+  hipLaunchKernelGGL(apply_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, rows, ns, partial_dev, scale, lv, tg, off, m_dev, v_dev, (float)a, beta1, beta2, eps,
+                     tau, stats_dev);
+  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+}
+
+}  // extern "C"

@@ -669,6 +669,37 @@ class TRPO:
                 raise RuntimeError("CassieTrpoSamplerStep failed (%d)" % rc)
         return book
 
+    def _book_step(self, book, rew, done, rew_row, t_row, cut_row, ep):
+        """Clocks, returns, truncation and episode statistics of one Env.step (shared with ddpg.DDPG): this step's rows rew_row / t_row / cut_row
+        are written, ep += (finished paths, their summed returns).  Returns (cut, done)."""
+        if book is not None and rew.dtype == torch.float64 and done.dtype == torch.uint8:
+            # clocks, returns, truncation and episode statistics of this step in ONE launch (CassieTrpoSamplerStep)
+            book(rew, done, rew_row, t_row, cut_row)
+            ep += self._book_partial.sum(0)
+            return cut_row, done
+        done = done.bool().clone()
+        rew_row[:], t_row[:] = rew, self.path_t
+        self.path_ret += rew
+        self.path_t += 1
+        cut = done | (self.path_t >= self.max_path_length)  # rllab truncates paths at max_path_length
+        cut_row[:] = cut
+        ep[0] += cut.sum()
+        ep[1] += torch.where(cut, self.path_ret, torch.zeros_like(self.path_ret)).sum()
+        self.path_ret = torch.where(cut, torch.zeros_like(self.path_ret), self.path_ret)
+        self.path_t = torch.where(cut, torch.zeros_like(self.path_t), self.path_t)
+        return cut, done
+
+    def _reset_truncated(self, cut, done, nobs):
+        """The masked reset of paths cut at max_path_length while their env is alive (armed by _steps_to_trunc); returns the next observation."""
+        self._steps_to_trunc -= 1
+        if self.env_reset_masked is not None and self._steps_to_trunc <= 0:
+            # a path may have been truncated at max_path_length while its env is still alive: rllab resets the env there
+            trunc = cut & ~done.bool()
+            if bool(trunc.any()):
+                nobs = self.env_reset_masked(trunc.to(torch.uint8))
+            self._steps_to_trunc = self.max_path_length - int(self.path_t.max())  # re-arm from the oldest live path
+        return nobs
+
     # ---- sampling: T vectorised Env.steps, everything stays on the device
     @torch.no_grad()
     def collect(self):
@@ -703,29 +734,8 @@ class TRPO:
                 a, mean, log_std = self.policy.get_actions(o, noise=noise)
                 nobs, rew, done = self.env_step(self.act_map(a))
                 obs_b[t], act_b[t], mean_b[t], lstd_b[t] = o, a, mean, log_std
-            if book is not None and rew.dtype == torch.float64 and done.dtype == torch.uint8:
-                # clocks, returns, truncation and episode statistics of this step in ONE launch (CassieTrpoSamplerStep)
-                book(rew, done, rew_b[t], t_b[t], done_b[t])
-                ep += self._book_partial.sum(0)
-                cut = done_b[t]
-            else:
-                done = done.bool().clone()
-                rew_b[t], t_b[t] = rew, self.path_t
-                self.path_ret += rew
-                self.path_t += 1
-                cut = done | (self.path_t >= self.max_path_length)  # rllab truncates paths at max_path_length
-                done_b[t] = cut
-                ep[0] += cut.sum()
-                ep[1] += torch.where(cut, self.path_ret, torch.zeros_like(self.path_ret)).sum()
-                self.path_ret = torch.where(cut, torch.zeros_like(self.path_ret), self.path_ret)
-                self.path_t = torch.where(cut, torch.zeros_like(self.path_t), self.path_t)
-            self._steps_to_trunc -= 1
-            if self.env_reset_masked is not None and self._steps_to_trunc <= 0:
-                # a path may have been truncated at max_path_length while its env is still alive: rllab resets the env there
-                trunc = cut & ~done.bool()
-                if bool(trunc.any()):
-                    nobs = self.env_reset_masked(trunc.to(torch.uint8))
-                self._steps_to_trunc = self.max_path_length - int(self.path_t.max())  # re-arm from the oldest live path
+            cut, done = self._book_step(book, rew, done, rew_b[t], t_b[t], done_b[t], ep)
+            nobs = self._reset_truncated(cut, done, nobs)
             self.obs = nobs.clone()
         return dict(obs=obs_b, act=act_b, mean=mean_b, log_std=lstd_b, rew=rew_b, done=done_b, t=t_b,
                     episode_count=ep[0], episode_return_sum=ep[1])
@@ -929,6 +939,8 @@ class TRPO:
     def _load_fields(self, ck):
         """Called with the loaded snapshot before anything is restored: refuses a snapshot that is not this run's (a subclass also takes
         back its _snapshot_fields()).  TRPO: the policy's hidden sizes must match (a snapshot without them was written by a 32 x 32 run)."""
+        if ck.get("algo") == "ddpg":   # its "policy" is a deterministic actor, not a GaussianMLPPolicy
+            raise ValueError("TRPO.load: the snapshot was written by ddpg, this run is trpo")
         theirs, mine = tuple(ck.get("hidden_sizes", (32, 32))), hidden_sizes_of(self.policy)
         if theirs != mine:
             raise ValueError("TRPO.load: the snapshot's policy has hidden sizes %r, this run's has %r" % (theirs, mine))

@@ -147,6 +147,52 @@ int CassiePgSurrogate(const float* obs_dev, int n, int obs_dim, int act_dim, con
 int CassiePgCgUpdate(int n, int ls_off, int n_ls, const float* Ap_mean_dev, const float* hls_dev, float reg, float tol, float* x_dev, float* r_dev, float* p_dev,
                      float* scal_dev, void* stream);
 
+/* ---- DDPG (cassierl_amd/ddpg.py, csrc/tu_ddpg.hip; rllab/envs/ddpg_cassie.py): 32 x 32 ReLU networks, float32, row-major as torch.nn.Linear
+ * stores them.  Actor mu(s) = tanh(W3 relu(W2 relu(W1 s + b1) + b2) + b3) with W1 [32][obs_dim], W2 [32][32], W3 [act_dim][32]; critic
+ * Q(s, a) = W3 relu(W2 [relu(W1 s + b1); a] + b2) + b3 with W1 [32][obs_dim], W2 [32][32 + act_dim], W3 [1][32].  A network is passed as a HOST
+ * array of its six device pointers {W1, b1, W2, b2, W3, b3}.  The replay pool is a structure of arrays on the device: obs [capacity][obs_dim],
+ * act [capacity][act_dim], rew [capacity], term [capacity] (0 or 1), next_obs [capacity][obs_dim].  Shapes: obs_dim 26 or 17, act_dim 6 or 7
+ * (the policy step: obs_dim 26); CASSIE_EINVAL otherwise. */
+#define CASSIE_DDPG_ACTOR 0
+#define CASSIE_DDPG_CRITIC 1
+
+/* parameters of the actor (which = CASSIE_DDPG_ACTOR) or the critic (CASSIE_DDPG_CRITIC); 0 for an unsupported shape */
+int CassieDdpgParamCount(int obs_dim, int act_dim, int which);
+/* rows of partial sums a gradient launch over `batch` samples writes (one per workgroup, at most 256) */
+int CassieDdpgPartialRows(int batch);
+
+/* One policy step for n environments in one launch (rllab's DeterministicMLPPolicy + OUStrategy + normalize()): obs float64 [n][obs_dim] ->
+ *   pool_obs_row [n][obs_dim] = its float32 image;  x = path_t[i] == 0 ? ou_mu : ou_state[i];  x += ou_theta (ou_mu - x) + ou_sigma noise[i];
+ *   ou_state[i] = x;  pool_act_row [n][act_dim] = clip(mu(obs) + x, -1, 1);  env_actions float64 = clip(low + (act + 1) / 2 (high - low), low, high).
+ * pool_obs_row / pool_act_row point at row `top` of the pool's obs / act arrays: the caller guarantees top + n <= capacity. */
+int CassieDdpgPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                         const float* b3, const float* noise_dev, const long long* path_t_dev, float ou_theta, float ou_sigma, float ou_mu, float* ou_state_dev,
+                         const double* low_dev, const double* high_dev, float* pool_obs_row_dev, float* pool_act_row_dev, double* env_actions_dev, void* stream);
+
+/* After Env.step, one launch: rew_row[i] = (float)(scale_reward * rew[i]), term_row[i] = done[i] != 0, next_obs_row = (float) next_obs, into the
+ * rows the policy step opened (pointers at row `top` of the pool's rew / term / next_obs arrays). */
+int CassieDdpgPoolCommit(const double* rew_dev, const unsigned char* done_dev, const double* next_obs_dev, int n, int obs_dim, double scale_reward,
+                         float* pool_rew_row_dev, float* pool_term_row_dev, float* pool_next_obs_row_dev, void* stream);
+
+/* Critic gradient on the batch idx [batch] (int64 pool rows, clamped to [0, pool_capacity)): y = rew + (1 - term) discount Q'(s', mu'(s')),
+ * e = Q(s, a) - y;  partial [CassieDdpgPartialRows(batch)][CassieDdpgParamCount(critic) + 2]: gradient of SUM e^2 in the order
+ * [gW1 | gb1 | gW2 | gb2 | gW3 | gb3], then sum e^2 and sum Q(s, a). */
+int CassieDdpgCriticGrad(const float* pool_obs, const float* pool_act, const float* pool_rew, const float* pool_term, const float* pool_next_obs,
+                         long long pool_capacity, const long long* idx_dev, int batch, int obs_dim, int act_dim,
+                         const float* const* target_actor, const float* const* target_critic, const float* const* critic, float discount, float* partial_dev,
+                         void* stream);
+
+/* Actor gradient on the same batch: partial [rows][CassieDdpgParamCount(actor) + 1]: gradient of -SUM Q(s, mu(s)) with respect to the actor through
+ * the critic as it is NOW (call it after the critic's CassieDdpgApply), then sum Q(s, mu(s)). */
+int CassieDdpgActorGrad(const float* pool_obs, long long pool_capacity, const long long* idx_dev, int batch, int obs_dim, int act_dim, const float* const* actor,
+                        const float* const* critic, float* partial_dev, void* stream);
+
+/* One launch, one workgroup: g = scale * (the `rows` partial rows added in order);  Lasagne's Adam (CassiePgAdam's formula, t = the step count
+ * after its increment) on the live network `which`;  target <- (1 - tau) target + tau live;  stats_dev[k] += the summed k-th column behind the
+ * gradient (float64; 2 columns for the critic, 1 for the actor; NULL: not recorded).  m_dev / v_dev: [CassieDdpgParamCount] in the row's order. */
+int CassieDdpgApply(int rows, int obs_dim, int act_dim, int which, const float* partial_dev, float scale, float* const* live, float* const* target, float* m_dev,
+                    float* v_dev, int t, float lr, float beta1, float beta2, float eps, float tau, double* stats_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

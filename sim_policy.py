@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Counterpart of rllab/envs/sim_policy.py:19-31 on the batched MI355X environment: load a snapshot written by train_trpo.py or
-train_vpg.py (`--snapshot`, snapshot_mode="last"; a VPG snapshot carries its policy's hidden sizes) and roll the policy out -- no training.  The reference animates ONE env through rllab's
+"""Counterpart of rllab/envs/sim_policy.py:19-31 on the batched MI355X environment: load a snapshot written by train_trpo.py,
+train_vpg.py or train_ddpg.py (`--snapshot`, snapshot_mode="last"; a VPG snapshot carries its policy's hidden sizes, a DDPG snapshot is rolled out with mu(s)) and roll the policy out -- no training.  The reference animates ONE env through rllab's
 `rollout(env, policy, max_path_length, animated=True)`; here N resident envs run the same loop in parallel (there is no
 viewer: GUI is out of scope) and the script prints what the reference's loop would let one read off the screen: path
 lengths and returns.
@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("file", help="snapshot written by train_trpo.py or train_vpg.py --snapshot")
+    ap.add_argument("file", help="snapshot written by train_trpo.py, train_vpg.py or train_ddpg.py --snapshot")
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--max-path-length", type=int, default=1000)   # sim_policy.py:14 default
     ap.add_argument("--kind", default="walk", choices=["walk", "stand"])
@@ -41,6 +41,11 @@ def main():
         from cassierl_amd.vpg import make_cassie_vpg
         algo = make_cassie_vpg(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
                                terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (32, 32))))
+    elif ck.get("algo") == "ddpg":   # a train_ddpg.py snapshot: the deterministic actor mu(s); only the policy is loaded, so the smallest pool will do
+        from cassierl_amd.ddpg import make_cassie_ddpg
+        algo = make_cassie_ddpg(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
+                                terrain=terrain, replay_pool_size=args.envs)
+        args.deterministic = True
     else:   # a train_trpo.py snapshot: 32 x 32 unless it records other hidden sizes
         algo = make_cassie_trpo(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
                                 terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (32, 32))))
@@ -54,7 +59,7 @@ def main():
     length = torch.zeros(n, dtype=torch.int64, device=obs.device)
     with torch.no_grad():
         for t in range(args.max_path_length):     # rllab.sampler.utils.rollout: until done or max_path_length
-            mean, log_std = pol.dist_info(obs.to(dt))
+            mean, log_std = (pol(obs.to(dt)), None) if args.deterministic and not hasattr(pol, "dist_info") else pol.dist_info(obs.to(dt))
             a = mean if args.deterministic else mean + R.counter_normal(args.seed, algo.env_ids, t, mean.shape[1]).to(dt) * log_std.exp()
             obs, rew, done = algo.env_step(algo.act_map(a))
             ret += torch.where(alive, rew, torch.zeros_like(rew))
