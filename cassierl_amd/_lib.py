@@ -35,6 +35,8 @@ EXPORTS = [
     "CassiePgFvp", "CassiePgSurrogateRows", "CassiePgSurrogate", "CassiePgCgUpdate",
     # DDPG (include/cassie_trpo.h)
     "CassieDdpgParamCount", "CassieDdpgPartialRows", "CassieDdpgPolicyStep", "CassieDdpgPoolCommit", "CassieDdpgCriticGrad", "CassieDdpgActorGrad", "CassieDdpgApply",
+    # PPO (include/cassie_trpo.h)
+    "CassieTrpoGae", "CassieTrpoClipGradRows", "CassieTrpoClipGrad", "CassiePgClipGradRows", "CassiePgClipGrad",
 ]
 
 

@@ -1,0 +1,369 @@
+"""PPO over the batched environment: the clipped surrogate, GAE(lambda) advantages and several epochs of minibatch Adam steps per rollout.
+
+There is no reference counterpart (rllab's own PPO is the KL-penalised L-BFGS variant and no script of the reference uses it): the torch
+statements in this module are the specification, the kernels of csrc/tu_ppo.hip evaluate them.
+
+  advantages  per environment column of the [T][N] batch, backwards, float64 (gae_advantages; CassieTrpoGae):
+                live = 1 - cut;  delta = r + gamma live V(s') - V(s);  adv = delta + gamma lambda live adv';  returns as TRPO's.
+              V is the LinearFeatureBaseline; a path cut at max_path_length is terminal, as for TRPO and VPG.  Centring and the baseline
+              fit are TRPO.process's.
+  loss        of one minibatch of M samples (all ranks together), ratio = exp(ll_new(a) - ll_old(a))  (ppo_loss):
+                L = -(1/M) sum min(ratio adv, clip(ratio, 1 - eps, 1 + eps) adv) - entropy_coeff sum_a (log_std_a + 0.5 log(2 pi e))
+  gradient    in closed form (clipped_grad_closed_form; CassieTrpoClipGrad / CassiePgClipGrad evaluate it in one launch):
+                clipped = (adv > 0 and ratio > 1 + eps) or (adv < 0 and ratio < 1 - eps);  w = clipped ? 0 : ratio adv;  z = (a - mean) / std
+                dL/dmean = -(1/M) w z / std;   dL/dlog_std = -(1/M) sum_s w (z^2 - 1) - entropy_coeff
+  update      `epochs` passes over the rollout; per pass a fresh device permutation, minibatch j = rows perm[j m : (j + 1) m] with
+              m = minibatch_size / world; per minibatch: gradient -> mean over ranks -> one Lasagne Adam step (vpg.adam_step_ / CassiePgAdam),
+              the Adam state kept across minibatches and iterations.  Nothing is read back inside the loop.  As for DDPG, the result depends
+              on the number of ranks unless minibatch_size equals the batch (each rank permutes its own shard).
+
+The sampler, exploration noise, baseline kernels and snapshot machinery are TRPO's (cassierl_amd/trpo.py), unchanged.
+"""
+import math
+
+import torch
+import torch.distributed as dist
+
+from . import terrain as terrain_lib
+from .trpo import (TRPO, AnalyticFisher, GaussianMLPPolicy, LinearFeatureBaseline, NormalizedActions, _world, all_mean_, all_sum_, broadcast_initial_policy,
+                   flat_grad, flat_params, hidden_sizes_of, set_flat_params)
+from .vpg import _MEAN_ORDER, _two_layer_tanh, adam_step_, fused_adam_step_
+
+
+# --------------------------------------------------------------------------------------------- the torch statements
+def gae_advantages(rew, cut, values, last_value, gamma, lam):
+    """rew, cut, values: [T, N] (values = V of every sample of the batch); last_value [N] = V of the observation after the last step.
+    Returns (returns, adv), both [T, N]: the torch statement of CassieTrpoGae."""
+    T = rew.shape[0]
+    returns, adv = torch.zeros_like(rew), torch.zeros_like(rew)
+    run, v_next, a_next = last_value.clone(), last_value, torch.zeros_like(rew[0])
+    for t in range(T - 1, -1, -1):
+        live = (~cut[t].bool()).to(rew.dtype)
+        run = rew[t] + gamma * run * live
+        delta = rew[t] + gamma * live * v_next - values[t]
+        a_next = delta + gamma * lam * live * a_next
+        returns[t], adv[t] = run, a_next
+        v_next = values[t]
+    return returns, adv
+
+
+def _old_ls_vector(old_log_std):
+    return old_log_std if old_log_std.dim() == 1 else old_log_std[0]
+
+
+def surrogate_terms(mean, log_std, act, adv, old_mean, old_log_std, clip):
+    """Per sample: (min(ratio adv, clip(ratio) adv), ratio, clipped flag) of the Gaussian (mean, log_std [A]) against the old one."""
+    ll_new = GaussianMLPPolicy.log_likelihood(act, mean, log_std)
+    ll_old = GaussianMLPPolicy.log_likelihood(act, old_mean, old_log_std)
+    ratio = (ll_new - ll_old).exp()
+    sur = torch.minimum(ratio * adv, ratio.clamp(1.0 - clip, 1.0 + clip) * adv)
+    clipped = ((adv > 0) & (ratio > 1.0 + clip)) | ((adv < 0) & (ratio < 1.0 - clip))
+    return sur, ratio, clipped
+
+
+def ppo_loss(policy, obs, act, adv, old_mean, old_log_std, clip, entropy_coeff):
+    """The loss of one minibatch (its rows are the M samples) through autograd: any dtype, any device."""
+    mean = policy.mean_net(obs)
+    sur, _, _ = surrogate_terms(mean, policy.log_std, act, adv, old_mean, _old_ls_vector(old_log_std), clip)
+    entropy = (policy.log_std + 0.5 * math.log(2.0 * math.pi * math.e)).sum()
+    return -sur.mean() - entropy_coeff * entropy
+
+
+def minibatch_stats(policy, obs, act, adv, old_mean, old_log_std, clip):
+    """[3] float64 sums over the rows: -min(..) (the loss without the entropy term), KL(old || new), clipped samples."""
+    with torch.no_grad():
+        mean, ls_old = policy.mean_net(obs), _old_ls_vector(old_log_std)
+        sur, _, clipped = surrogate_terms(mean, policy.log_std, act, adv, old_mean, ls_old, clip)
+        kl = GaussianMLPPolicy.kl(old_mean, ls_old, mean, policy.log_std)
+        return torch.stack([-sur.double().sum(), kl.double().sum(), clipped.double().sum()])
+
+
+def clipped_grad_closed_form(policy, obs, act, adv, old_mean, old_log_std, clip, entropy_coeff, scale=None):
+    """The gradient of ppo_loss in closed form (what the kernels evaluate), flat in parameter order; scale = 1 / M (default: the rows given).
+    The mean network's part J' (dL/dmean) comes from AnalyticFisher's reverse pass at the policy's CURRENT parameters."""
+    with torch.no_grad():
+        scale = 1.0 / obs.shape[0] if scale is None else scale
+        fisher = AnalyticFisher(policy, obs)
+        mean = policy.mean_net(obs)
+        _, ratio, clipped = surrogate_terms(mean, policy.log_std, act, adv, old_mean, _old_ls_vector(old_log_std), clip)
+        w = torch.where(clipped, torch.zeros_like(ratio), ratio * adv).unsqueeze(-1)
+        std = policy.log_std.detach().exp()
+        z = (act - mean) / std
+        g = fisher.vjp(-scale * w * z / std)
+        g_ls = -scale * (w * (z * z - 1.0)).sum(0) - entropy_coeff
+        i0 = 0
+        for nm, p in policy.named_parameters():
+            if nm == "log_std":
+                g[i0:i0 + p.numel()] += g_ls.to(g.dtype)
+            i0 += p.numel()
+    return g
+
+
+def aligned_flat_params(policy):
+    """flat_params(policy) in a buffer whose mean-network part starts on a 16-byte boundary (the width-128 kernels read b1, W2, b2, W3 as
+    float4, and log_std -- 6 or 7 floats -- sits in front of them in the flat vector): pointers into it reach the kernels as they are."""
+    theta = flat_params(policy)
+    first = 0
+    for nm, p in policy.named_parameters():
+        if nm == _MEAN_ORDER[0]:
+            break
+        first += p.numel()
+    pad = (-first) % 4
+    buf = torch.empty(pad + theta.numel(), dtype=theta.dtype, device=theta.device)
+    out = buf[pad:]
+    out.copy_(theta)
+    return out
+
+
+class ClipGradKernels:
+    """The gradient of ppo_loss on minibatches of one batch, at the parameters in `theta` (a flat vector in parameter order that the caller
+    updates in place: aligned_flat_params): width 32 -> CassieTrpoClipGrad, width 128 -> CassiePgClipGrad, one launch each; CPU tensors,
+    other shapes, fused=False or a library without the symbols -> autograd of ppo_loss.  `kind`: "trpo_clip", "pg_clip" or "autograd"."""
+
+    def __init__(self, policy, theta, obs, act, adv, old_mean, old_log_std, clip, entropy_coeff, fused=True):
+        self.policy, self.theta, self.clip, self.entropy_coeff = policy, theta, float(clip), float(entropy_coeff)
+        self.obs, self.act, self.adv, self.old_mean = obs, act, adv, old_mean
+        self.old_ls = _old_ls_vector(old_log_std).detach().clone().contiguous()
+        self.kind = "autograd"
+        lin = _two_layer_tanh(policy)
+        if not fused or lin is None or not obs.is_cuda or obs.dtype != torch.float32 or theta.dtype != torch.float32:
+            return
+        hs = hidden_sizes_of(policy)
+        entry = {(32, 32): ("CassieTrpoClipGrad", "CassieTrpoClipGradRows", "CassieTrpoParamCount", "trpo_clip"),
+                 (128, 128): ("CassiePgClipGrad", "CassiePgClipGradRows", "CassiePgParamCount", "pg_clip")}.get(hs)
+        if entry is None:
+            return
+        import ctypes as ct
+        from . import _lib
+        try:
+            L = _lib.load()
+        except OSError:
+            return
+        if not hasattr(L, entry[0]):
+            return
+        D, A, H = lin[0].in_features, lin[2].out_features, hs[0]
+        NP = getattr(L, entry[2])(D, A)
+        if NP == 0:
+            return
+        self.L, self.ct, self.D, self.A, self.NP = L, ct, D, A, NP
+        self._entry, self._rows = getattr(L, entry[0]), getattr(L, entry[1])
+        self.obs, self.act, self.adv, self.old_mean = obs.contiguous(), act.contiguous(), adv.to(torch.float32).contiguous(), old_mean.contiguous()
+        # where every parameter sits in theta, and the permutation from a partial row [gW1 | gb1 | gW2 | gb2 | gW3 | gb3 | g_log_std] to it
+        sizes = dict(zip(_MEAN_ORDER, [H * D, H, H * H, H, A * H, A]))
+        sizes["log_std"] = A
+        korder, koff, o = _MEAN_ORDER + ["log_std"], {}, 0
+        for nm in korder:
+            koff[nm] = o
+            o += sizes[nm]
+        self.off, gather, o = {}, [], 0
+        for nm, p in policy.named_parameters():
+            if nm not in sizes or p.numel() != sizes[nm]:
+                return
+            self.off[nm] = o
+            gather.append(torch.arange(koff[nm], koff[nm] + sizes[nm]))
+            o += p.numel()
+        if len(self.off) != len(korder):
+            return
+        dev = obs.device
+        self.gather = torch.cat(gather).to(dev)
+        self.ent = None
+        if self.entropy_coeff != 0.0:
+            self.ent = torch.zeros(o, dtype=torch.float32, device=dev)
+            self.ent[self.off["log_std"]:self.off["log_std"] + A] = -self.entropy_coeff
+        self._bufs = {}
+        self.kind = entry[3]
+
+    def _fused(self, idx, m, scale, stats_out):
+        ct, n = self.ct, self.obs.shape[0]
+        rows = self._rows(m)
+        if rows not in self._bufs:
+            self._bufs[rows] = (torch.empty((rows, self.NP + self.A), dtype=torch.float32, device=self.obs.device),
+                                torch.empty((rows, 3), dtype=torch.float64, device=self.obs.device))
+        partial, stats = self._bufs[rows]
+        P = lambda t: ct.c_void_p(t.data_ptr())
+        base = self.theta.data_ptr()
+        W = [ct.c_void_p(base + 4 * self.off[k]) for k in _MEAN_ORDER]
+        if idx is not None:
+            assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == m
+        rc = self._entry(P(self.obs), n, self.D, self.A, *W, None if idx is None else P(idx), m, P(self.act), P(self.adv), P(self.old_mean), P(self.old_ls),
+                         ct.c_void_p(base + 4 * self.off["log_std"]), ct.c_float(self.clip), ct.c_float(scale), P(partial), P(stats),
+                         ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream))
+        if rc != 0:
+            raise RuntimeError("%s failed (%d)" % (self._entry.__name__, rc))
+        g = partial.sum(0)[self.gather]
+        if self.ent is not None:
+            g += self.ent
+        if stats_out is None:
+            return g, stats.sum(0)
+        torch.sum(stats, 0, out=stats_out)
+        return g, stats_out
+
+    def grad(self, idx=None, m=None, stats_out=None):
+        """(gradient of the minibatch's loss with 1/M = 1/m, flat in parameter order; [3] float64 sums of minibatch_stats) for the rows
+        idx [m] of the batch (None: rows 0 .. m - 1, m = the batch by default) at the parameters in theta."""
+        m = (self.obs.shape[0] if idx is None else idx.numel()) if m is None else m
+        if self.kind != "autograd":
+            return self._fused(idx, m, 1.0 / m, stats_out)
+        pol = self.policy
+        set_flat_params(pol, self.theta)
+        sl = slice(0, m) if idx is None else idx
+        rows = [x[sl] for x in (self.obs, self.act, self.adv, self.old_mean)]
+        g = flat_grad(ppo_loss(pol, *rows, self.old_ls, self.clip, self.entropy_coeff), pol).detach()
+        st = minibatch_stats(pol, *rows, self.old_ls, self.clip)
+        if stats_out is not None:
+            stats_out.copy_(st)
+            st = stats_out
+        return g, st
+
+
+# --------------------------------------------------------------------------------------------- PPO
+class PPO(TRPO):
+    """PPO on TRPO's sampler and baseline.  Switches (attributes, default True) that tests set to force the torch path: fused_policy_step,
+    fused_gae (CassieTrpoGae), fused_grad (ClipGradKernels), fused_adam (CassiePgAdam).  last_grad_kind says which gradient ran."""
+
+    def __init__(self, env_step, env_reset, policy, baseline, n_envs, obs_dim, act_map, batch_size=10000, max_path_length=1000, discount=0.99,
+                 learning_rate=3e-4, clip_range=0.2, gae_lambda=0.95, epochs=4, minibatch_size=None, entropy_coeff=0.0, beta1=0.9, beta2=0.999,
+                 epsilon=1e-8, seed=1, env_reset_masked=None, env_id0=None):
+        super().__init__(env_step, env_reset, policy, baseline, n_envs, obs_dim, act_map, batch_size=batch_size, max_path_length=max_path_length,
+                         discount=discount, seed=seed, env_reset_masked=env_reset_masked, env_id0=env_id0)
+        self.learning_rate, self.beta1, self.beta2, self.epsilon = learning_rate, beta1, beta2, epsilon
+        self.clip_range, self.gae_lambda, self.epochs, self.entropy_coeff = clip_range, gae_lambda, int(epochs), entropy_coeff
+        world, n_local = _world(), self.horizon * n_envs
+        self.minibatch_size = n_local * world // 4 if minibatch_size is None else int(minibatch_size)
+        self._check_minibatch(n_local)
+        self.adam_t, self.adam_m, self.adam_v = 0, None, None
+        self.last_grad_kind = None
+        dev = next(policy.parameters()).device
+        rank = dist.get_rank() if dist.is_initialized() else 0
+        self.gen_mb = torch.Generator(device=dev)   # the minibatch permutations of this rank's shard
+        self.gen_mb.manual_seed(seed * 1000003 + 7919 * (rank + 1))
+
+    def _check_minibatch(self, n_local):
+        world = _world()
+        if self.epochs < 1 or self.minibatch_size < 1 or self.minibatch_size % world != 0:
+            raise ValueError("PPO: minibatch_size %d must be a positive multiple of the %d ranks (epochs %d >= 1)" % (self.minibatch_size, world, self.epochs))
+        m = self.minibatch_size // world
+        if n_local % m != 0:
+            raise ValueError("PPO: a rank's %d samples per iteration are not a multiple of its minibatch of %d (minibatch_size %d over %d ranks)"
+                             % (n_local, m, self.minibatch_size, world))
+        return m
+
+    @property
+    def hidden_sizes(self):
+        return hidden_sizes_of(self.policy)
+
+    def process(self, batch):
+        """TRPO.process with GAE(lambda) advantages: centring over ranks and the baseline fit follow it line by line."""
+        T, N = batch["rew"].shape
+        flat = lambda x: x.reshape(T * N, *x.shape[2:])
+        obs, tt = flat(batch["obs"]), flat(batch["t"])
+        bk = self._baseline_kernels(obs)
+        coeffs = self.baseline.coeffs
+        if bk is not None and getattr(self, "fused_gae", True):
+            last_v = None if coeffs is None else bk.predict(self.obs.to(obs.dtype), self.path_t, coeffs)
+            returns, adv, sums = bk.gae(batch["obs"], batch["t"], batch["rew"], batch["done"], coeffs, last_v, self.discount, self.gae_lambda)
+            adv = flat(adv)
+            self.last_gae_fused = True
+        else:
+            if bk is not None and coeffs is not None:
+                last_v, values = bk.predict(self.obs.to(obs.dtype), self.path_t, coeffs), bk.predict(obs, tt, coeffs).view(T, N)
+            else:
+                last_v, values = self.baseline.predict(self.obs.to(obs.dtype), self.path_t), self.baseline.predict(obs, tt).view(T, N)
+            returns, adv = gae_advantages(batch["rew"], batch["done"], values, last_v, self.discount, self.gae_lambda)
+            adv = flat(adv)
+            sums = torch.stack([adv.sum(), (adv * adv).sum()])
+            self.last_gae_fused = False
+        n = torch.tensor([adv.numel()], dtype=torch.float64, device=adv.device)
+        s12 = all_sum_(sums.clone(), "advantage_all_reduce"); n = all_sum_(n, "advantage_all_reduce")
+        mean = s12[0] / n
+        std = (s12[1] / n - mean * mean).clamp_min(0).sqrt()
+        adv = ((adv - mean) / (std + 1e-8)).to(obs.dtype)  # center_adv
+        if bk is not None:
+            A, b = bk.gram(obs, tt, flat(returns))
+            self.baseline.fit_normal_equations(A, b, bk.ridge_solve if getattr(self, "fused_solve", True) else None)
+        else:
+            self.baseline.fit(obs, tt, flat(returns))
+        return dict(obs=obs, act=flat(batch["act"]), mean=flat(batch["mean"]), log_std=flat(batch["log_std"]), adv=adv)
+
+    def optimize(self, d):
+        pol = self.policy
+        obs, act, adv, old_mean, old_lstd = d["obs"], d["act"], d["adv"], d["mean"], d["log_std"]
+        n_local, world = obs.shape[0], _world()
+        m = self._check_minibatch(n_local)
+        nmb = n_local // m
+        theta = aligned_flat_params(pol)
+        ck = ClipGradKernels(pol, theta, obs, act, adv, old_mean, old_lstd, self.clip_range, self.entropy_coeff, fused=getattr(self, "fused_grad", True))
+        self.last_grad_kind = ck.kind
+        if self.adam_m is None:
+            self.adam_m, self.adam_v = torch.zeros_like(theta), torch.zeros_like(theta)
+        fused_adam = getattr(self, "fused_adam", True) and theta.is_cuda and theta.dtype == torch.float32
+        step = fused_adam_step_ if fused_adam else adam_step_
+        self.last_adam_fused = fused_adam
+        # per minibatch step (loss sum, KL sum, clipped samples, gradient norm), kept on the device and read once behind the loop
+        acc = torch.zeros((self.epochs * nmb, 4), dtype=torch.float64, device=obs.device)
+        self.last_perms = []
+        k = 0
+        for _ in range(self.epochs):
+            perm = torch.randperm(n_local, generator=self.gen_mb, device=obs.device)
+            if getattr(self, "keep_perms", False):
+                self.last_perms.append(perm)
+            for j in range(nmb):
+                idx = perm[j * m:(j + 1) * m]
+                g, _ = ck.grad(idx, stats_out=acc[k, :3])
+                g = all_mean_(g.contiguous(), "gradient_all_reduce")
+                acc[k, 3] = torch.linalg.vector_norm(g, dtype=torch.float64)
+                self.adam_t += 1
+                step(theta, g.to(theta.dtype), self.adam_m, self.adam_v, self.adam_t, self.learning_rate, self.beta1, self.beta2, self.epsilon)
+                k += 1
+        set_flat_params(pol, theta)
+        M = float(m * world)
+        ent = self.entropy_coeff * float(pol.log_std.numel()) * 0.5 * math.log(2.0 * math.pi * math.e)   # (the log_std part of the bonus is not logged)
+        sums = all_sum_(acc[:, :3].contiguous(), "stats_all_reduce")
+        rows = torch.cat([sums, acc[:, 3:]], dim=1).tolist()   # the one read-back
+        return dict(loss_first=rows[0][0] / M - ent, loss_last=rows[-1][0] / M - ent, mean_kl=sum(r[1] for r in rows) / (M * len(rows)),
+                    clip_frac=sum(r[2] for r in rows) / (M * len(rows)), grad_norm=sum(r[3] for r in rows) / len(rows), minibatch_steps=len(rows))
+
+    # ---- snapshot: TRPO's, plus the algorithm, the policy shape, the hyper-parameters, the Adam state and the permutation generator
+    def _snapshot_fields(self):
+        return dict(algo="ppo", hidden_sizes=list(self.hidden_sizes), learning_rate=float(self.learning_rate), clip_range=float(self.clip_range),
+                    gae_lambda=float(self.gae_lambda), epochs=int(self.epochs), minibatch_size=int(self.minibatch_size), entropy_coeff=float(self.entropy_coeff),
+                    adam_t=int(self.adam_t), adam_m=None if self.adam_m is None else self.adam_m.detach().cpu(),
+                    adam_v=None if self.adam_v is None else self.adam_v.detach().cpu(), gen_mb_state=self.gen_mb.get_state())
+
+    def _load_fields(self, ck):
+        algo = ck.get("algo", "trpo")
+        if algo != "ppo":
+            raise ValueError("PPO.load: the snapshot was written by %s, this run is ppo" % algo)
+        theirs, mine = tuple(ck.get("hidden_sizes", (32, 32))), self.hidden_sizes
+        if theirs != mine:
+            raise ValueError("PPO.load: the snapshot's policy has hidden sizes %r, this run's has %r" % (theirs, mine))
+        dev = next(self.policy.parameters()).device
+        self.adam_t = int(ck.get("adam_t", 0))
+        self.adam_m = None if ck.get("adam_m") is None else ck["adam_m"].to(dev)
+        self.adam_v = None if ck.get("adam_v") is None else ck["adam_v"].to(dev)
+        if ck.get("gen_mb_state") is not None:
+            self.gen_mb.set_state(ck["gen_mb_state"])
+
+
+def make_cassie_ppo(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, hidden_sizes=(128, 128), init_std=1.0, terrain=None,
+                    sync_policy=True, **kw):
+    """PPO on the batched MI355X environment; the counterpart of vpg.make_cassie_vpg (same env, terrain and sync_policy rules)."""
+    from .vec_env import CassieVecEnv
+    env = CassieVecEnv(n_envs, kind=kind, control_mode=control_mode, n_substeps=10, auto_reset=True, device=device, trajectory=trajectory)
+    env.use_torch_stream()
+    dev = "cuda:%d" % device
+    bufs = env.alloc()
+    torch.manual_seed(seed)
+    obs_w = env.observation_space.shape[0]
+    policy = GaussianMLPPolicy(obs_w, env.adim, tuple(hidden_sizes), init_std=init_std).to(dev)
+    act_map = NormalizedActions(env.action_space.low, env.action_space.high, dev)
+    algo = PPO(lambda a: env.step(a, bufs), lambda: env.reset(bufs), policy, LinearFeatureBaseline(), n_envs, obs_w, act_map, seed=seed,
+               env_reset_masked=lambda m: env.reset(bufs, mask=m), **kw)
+    algo.env = env
+    algo.terrain_spec = terrain
+    if terrain is not None:
+        env.set_terrain_library(terrain_lib.library_of_spec(terrain), terrain_lib.DEFAULT_SIZE[:2])
+        env.set_terrain_ids(terrain_lib.assign_terrains(terrain["seed"], algo.env_ids, len(terrain["files"])).to(dev))
+    if sync_policy:
+        broadcast_initial_policy(algo)
+    return algo

@@ -253,6 +253,20 @@ class BaselineKernels:
             raise RuntimeError("CassieTrpoReturnsAdvantages failed (%d)" % rc)
         return returns, adv, partial.sum(0)
 
+    def gae(self, obs_b, t_b, rew_b, cut_b, coeffs, last_value, gamma, lam):
+        """returns_advantages with GAE(lambda) advantages (CassieTrpoGae; cassierl_amd/ppo.py: gae_advantages is its torch statement)."""
+        T, n = rew_b.shape
+        assert obs_b.is_contiguous() and t_b.is_contiguous() and rew_b.is_contiguous() and cut_b.is_contiguous()
+        assert obs_b.dtype == torch.float32 and t_b.dtype == torch.int64 and rew_b.dtype == torch.float64 and cut_b.dtype in (torch.bool, torch.uint8)
+        returns, adv = torch.empty_like(rew_b), torch.empty_like(rew_b)
+        partial = torch.empty(((n + 255) // 256, 2), dtype=torch.float64, device=self.dev)
+        rc = self.L.CassieTrpoGae(self._p(obs_b), self._p(t_b), self._p(rew_b), self._p(cut_b), T, n, self.D,
+                                  self._p(None if coeffs is None else coeffs.contiguous()), self._p(None if last_value is None else last_value.contiguous()),
+                                  self.ct.c_double(gamma), self.ct.c_double(lam), self._p(returns), self._p(adv), self._p(partial), self._stream())
+        if rc != 0:
+            raise RuntimeError("CassieTrpoGae failed (%d)" % rc)
+        return returns, adv, partial.sum(0)
+
     def gram(self, obs32, t, y):
         """(X'X [F, F], X'y [F]) of the baseline's features on m samples."""
         m = obs32.shape[0]

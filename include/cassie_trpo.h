@@ -193,6 +193,38 @@ int CassieDdpgActorGrad(const float* pool_obs, long long pool_capacity, const lo
 int CassieDdpgApply(int rows, int obs_dim, int act_dim, int which, const float* partial_dev, float scale, float* const* live, float* const* target, float* m_dev,
                     float* v_dev, int t, float lr, float beta1, float beta2, float eps, float tau, double* stats_dev, void* stream);
 
+/* ---- PPO (cassierl_amd/ppo.py, csrc/tu_ppo.hip): GAE(lambda) advantages and the gradient of the clipped surrogate on a minibatch. */
+
+/* CassieTrpoReturnsAdvantages with GAE(lambda): backwards over the T steps of an environment's column, live = !cut[s],
+ *   V_next = value of the batch's own next row (last_value [n] behind the last step, NULL = 0),
+ *   delta = rew[s] + gamma live V_next - value,  adv[s] = delta + gamma lambda live adv[next step]  (0 behind the last step),
+ *   returns[s] as CassieTrpoReturnsAdvantages writes them (what the baseline is fitted to),
+ * and partial[(n + 255) / 256][2] = per workgroup (sum adv, sum adv^2), fixed order.  lambda = 1: adv = returns - value up to rounding. */
+int CassieTrpoGae(const float* obs_dev, const long long* t_dev, const double* rew_dev, const unsigned char* cut_dev, int T, int n, int obs_dim,
+                  const double* coeffs_dev, const double* last_value_dev, double gamma, double lambda, double* returns_dev, double* adv_dev, double* partial_dev,
+                  void* stream);
+
+/* Gradient of PPO's clipped surrogate on one minibatch, one launch: the forward pass of the mean network at the GIVEN weights on the m rows
+ * idx [m] of the batch (int64, clamped to [0, n); NULL = rows 0 .. m - 1, m <= n), then in registers
+ *   ratio = exp(ll_new(act) - ll_old(act)),  clipped = (adv > 0 and ratio > 1 + clip) or (adv < 0 and ratio < 1 - clip),  w = clipped ? 0 : ratio adv,
+ *   d L / d mean = -scale w z / std  (z = (act - mean) / std at the given weights and log_std_new),
+ * then the reverse pass of CassieTrpoVjp / CassiePgVjp.  obs [n][obs_dim], act / old_mean [n][act_dim], adv [n] are indexed by batch row;
+ * log_std_old / log_std_new [act_dim].  partial [rows][ParamCount + act_dim] float32 = [gW1 | gb1 | gW2 | gb2 | gW3 | gb3 | g_log_std] with
+ * g_log_std = -scale sum_s w (z^2 - 1) (an entropy bonus is a constant the caller adds); stats [rows][3] float64 = per row
+ * (sum_s -min(ratio adv, clip(ratio, 1 - clip, 1 + clip) adv), sum_s KL(old_s || new_s), number of clipped samples).  The caller adds the
+ * rows: CassieTrpoClipGradRows(m) of them, one per wavefront (width 32), CassiePgClipGradRows(m), one per workgroup (width 128, whose b1, W2,
+ * b2, W3 must be 16-byte aligned).  Every sum runs in a fixed order: a call repeats bit for bit. */
+int CassieTrpoClipGradRows(int m);
+int CassieTrpoClipGrad(const float* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2,
+                       const float* W3, const float* b3, const long long* idx_dev, int m, const float* act_dev, const float* adv_dev,
+                       const float* old_mean_dev, const float* log_std_old, const float* log_std_new, float clip, float scale, float* partial_dev,
+                       double* stats_dev, void* stream);
+int CassiePgClipGradRows(int m);
+int CassiePgClipGrad(const float* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2,
+                     const float* W3, const float* b3, const long long* idx_dev, int m, const float* act_dev, const float* adv_dev,
+                     const float* old_mean_dev, const float* log_std_old, const float* log_std_new, float clip, float scale, float* partial_dev,
+                     double* stats_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

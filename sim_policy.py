@@ -41,6 +41,10 @@ def main():
         from cassierl_amd.vpg import make_cassie_vpg
         algo = make_cassie_vpg(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
                                terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (32, 32))))
+    elif ck.get("algo") == "ppo":   # a train_ppo.py snapshot: the policy's shape comes from it; only the policy is loaded, so the batch shape is free
+        from cassierl_amd.ppo import make_cassie_ppo
+        algo = make_cassie_ppo(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
+                               terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (128, 128))), batch_size=args.envs, minibatch_size=args.envs)
     elif ck.get("algo") == "ddpg":   # a train_ddpg.py snapshot: the deterministic actor mu(s); only the policy is loaded, so the smallest pool will do
         from cassierl_amd.ddpg import make_cassie_ddpg
         algo = make_cassie_ddpg(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
