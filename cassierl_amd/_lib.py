@@ -35,6 +35,8 @@ EXPORTS = [
     "CassiePgFvp", "CassiePgSurrogateRows", "CassiePgSurrogate", "CassiePgCgUpdate",
     # DDPG (include/cassie_trpo.h)
     "CassieDdpgParamCount", "CassieDdpgPartialRows", "CassieDdpgPolicyStep", "CassieDdpgPoolCommit", "CassieDdpgCriticGrad", "CassieDdpgActorGrad", "CassieDdpgApply",
+    # SAC (include/cassie_trpo.h)
+    "CassieSacParamCount", "CassieSacPolicyStep", "CassieSacCriticGrad", "CassieSacActorGrad", "CassieSacApply",
     # PPO (include/cassie_trpo.h)
     "CassieTrpoGae", "CassieTrpoClipGradRows", "CassieTrpoClipGrad", "CassiePgClipGradRows", "CassiePgClipGrad",
 ]

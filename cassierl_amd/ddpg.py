@@ -304,6 +304,8 @@ class DDPG(TRPO):
     that tests set to force the torch statements: fused_policy_step (CassieDdpgPolicyStep + CassieDdpgPoolCommit), fused_update (the four update
     launches), fused_sampler_step (TRPO's).  last_update_kind says which update ran: "ddpg_kernels" or "torch"."""
 
+    _REW = 3   # _stats: sum (Q - y)^2, sum Q(s, a), sum Q(s, mu(s)), summed mean reward
+
     def __init__(self, env_step, env_reset, policy, qf, n_envs, obs_dim, act_map, batch_size=32, max_path_length=100, epoch_length=1000,
                  min_pool_size=10000, replay_pool_size=1000000, discount=0.99, scale_reward=0.01, qf_learning_rate=1e-3, policy_learning_rate=1e-4,
                  soft_target_tau=1e-3, updates_per_step=1, ou_theta=0.15, ou_sigma=0.3, ou_mu=0.0, beta1=0.9, beta2=0.999, epsilon=1e-8, seed=1,
@@ -311,23 +313,30 @@ class DDPG(TRPO):
         import copy
         super().__init__(env_step, env_reset, policy, _NoBaseline(), n_envs, obs_dim, act_map, batch_size=batch_size, max_path_length=max_path_length,
                          discount=discount, seed=seed, env_reset_masked=env_reset_masked, env_id0=env_id0)
-        world = _world()
-        if batch_size % world != 0:
-            raise ValueError("DDPG: batch_size (%d) must be divisible by the number of ranks (%d)" % (batch_size, world))
         self.qf = qf
         self.target_policy, self.target_qf = copy.deepcopy(policy), copy.deepcopy(qf)
         for p in list(self.target_policy.parameters()) + list(self.target_qf.parameters()):
             p.requires_grad_(False)
-        p0 = next(policy.parameters())
+        dev, dt = self._init_off_policy("DDPG", policy.l3.out_features, batch_size, epoch_length, min_pool_size, replay_pool_size, scale_reward, qf_learning_rate,
+                                        policy_learning_rate, soft_target_tau, updates_per_step, beta1, beta2, epsilon, seed, snapshot_pool)
+        self.ou = OUStrategy(n_envs, self.act_dim, dev, dt, ou_theta, ou_sigma, ou_mu)
+        self.adam_mu, self.adam_q = new_adam(policy), new_adam(qf)
+
+    def _init_off_policy(self, name, act_dim, batch_size, epoch_length, min_pool_size, replay_pool_size, scale_reward, qf_learning_rate, policy_learning_rate,
+                         soft_target_tau, updates_per_step, beta1, beta2, epsilon, seed, snapshot_pool):
+        """What every algorithm on the replay pool sets up after TRPO.__init__ (DDPG, SAC): this rank's share of the batch, the schedule, the pool, the
+        index generator's seeding and the per-iteration accumulators.  Returns the policy's (device, dtype)."""
+        world = _world()
+        if batch_size % world != 0:
+            raise ValueError("%s: batch_size (%d) must be divisible by the number of ranks (%d)" % (name, batch_size, world))
+        p0 = next(self.policy.parameters())
         dev, dt = p0.device, p0.dtype
         self.batch_size, self.batch_local = batch_size, batch_size // world
         self.epoch_length, self.min_pool_size, self.updates_per_step = epoch_length, min_pool_size, updates_per_step
         self.scale_reward, self.qf_learning_rate, self.policy_learning_rate, self.tau = scale_reward, qf_learning_rate, policy_learning_rate, soft_target_tau
         self.beta1, self.beta2, self.epsilon = beta1, beta2, epsilon
-        self.act_dim = policy.l3.out_features
-        self.pool = ReplayPool(replay_pool_size, n_envs, obs_dim, self.act_dim, dev, dt)
-        self.ou = OUStrategy(n_envs, self.act_dim, dev, dt, ou_theta, ou_sigma, ou_mu)
-        self.adam_mu, self.adam_q = new_adam(policy), new_adam(qf)
+        self.act_dim = act_dim
+        self.pool = ReplayPool(replay_pool_size, self.n_envs, self.obs_dim, act_dim, dev, dt)
         rank = dist.get_rank() if dist.is_initialized() else 0
         self.idx_gen = torch.Generator(device=dev)
         self.idx_gen.manual_seed(seed * 1000003 + 7919 * (rank + 1))
@@ -336,9 +345,10 @@ class DDPG(TRPO):
         self.last_update_kind = None
         self.last_policy_step_fused = None
         self._ep = torch.zeros(2, dtype=torch.float64, device=dev)        # finished paths, their summed returns (this iteration)
-        self._stats = torch.zeros(4, dtype=torch.float64, device=dev)     # sum (Q - y)^2, sum Q(s, a), sum Q(s, mu(s)), summed mean reward
+        self._stats = torch.zeros(self._REW + 1, dtype=torch.float64, device=dev)   # the update's sums (see _REW), then the summed mean reward
         self._rows = None
         self._kernels = None
+        return dev, dt
 
     # ---- kernels
     def _update_kernels(self):
@@ -382,13 +392,24 @@ class DDPG(TRPO):
             if rc != 0:
                 raise RuntimeError("CassieDdpgPolicyStep failed (%d)" % rc)
 
+        return step, self._pool_commit(commit_fn, stream)
+
+    def _pool_commit(self, commit_fn, stream):
+        """CassieDdpgPoolCommit on the rows the policy step opened."""
+        P = lambda t: ct.c_void_p(t.data_ptr())
+        pool, n, D = self.pool, self.n_envs, self.obs_dim
+
         def commit(rew, done, nobs, top):
             assert rew.is_contiguous() and done.is_contiguous() and nobs.is_contiguous() and nobs.dtype == torch.float64
             assert 0 <= top and top + n <= pool.capacity
             rc = commit_fn(P(rew), P(done), P(nobs), n, D, ct.c_double(self.scale_reward), P(pool.rew[top:]), P(pool.term[top:]), P(pool.nobs[top]), stream())
             if rc != 0:
                 raise RuntimeError("CassieDdpgPoolCommit failed (%d)" % rc)
-        return step, commit
+        return commit
+
+    def _explore(self, o, noise):
+        """The exploring action in [-1, 1] for the float32 observations o and this step's normals (the torch statement of the policy-step kernel)."""
+        return self.ou.get_action(self.policy(o), noise, self.path_t == 0)
 
     # ---- one vector step and its updates
     @torch.no_grad()
@@ -409,7 +430,7 @@ class DDPG(TRPO):
             nobs, rew, done = self.env_step(self._env_actions)
         else:
             o = self.obs.to(dt)
-            a = self.ou.get_action(self.policy(o), noise, self.path_t == 0)
+            a = self._explore(o, noise)
             nobs, rew, done = self.env_step(self.act_map(a))
         self.last_policy_step_fused = fused is not None
         if fused is not None and rew.dtype == torch.float64 and done.dtype == torch.uint8:
@@ -419,7 +440,7 @@ class DDPG(TRPO):
                 o, a = pool.obs[top:top + N], pool.act[top:top + N]
             pool.write(top, o, a, (self.scale_reward * rew.double()).to(dt), (done != 0).to(dt), nobs.to(dt))
         pool.advance()
-        self._stats[3] += rew.mean()
+        self._stats[self._REW] += rew.mean()
         book = self._fused_sampler_step(dev)
         cut, done = self._book_step(book, rew, done, *self._rows, self._ep)
         nobs = self._reset_truncated(cut, done, nobs)   # after the commit: a truncated path keeps its true s'

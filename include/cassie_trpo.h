@@ -193,6 +193,45 @@ int CassieDdpgActorGrad(const float* pool_obs, long long pool_capacity, const lo
 int CassieDdpgApply(int rows, int obs_dim, int act_dim, int which, const float* partial_dev, float scale, float* const* live, float* const* target, float* m_dev,
                     float* v_dev, int t, float lr, float beta1, float beta2, float eps, float tau, double* stats_dev, void* stream);
 
+/* ---- SAC (cassierl_amd/sac.py, csrc/tu_sac.hip): DDPG's 32 x 32 ReLU networks, shapes and replay pool.  The actor's output layer has
+ * 2 act_dim rows, W3 [2 act_dim][32]: mean = rows [0, act_dim), log_std = clamp(rows [act_dim, 2 act_dim), -20, 2); a sample is
+ * u = mean + exp(log_std) eps, a = tanh(u), log pi(a|s) = sum_k (-eps_k^2 / 2 - log_std_k - log(2 pi) / 2) - sum_k 2 (log 2 - u_k - softplus(-2 u_k)).
+ * The two critics are DDPG's critic: their parameter count is CassieDdpgParamCount(.., CASSIE_DDPG_CRITIC), the rows of partial sums of a batch
+ * CassieDdpgPartialRows(batch), their Adam step and soft update CassieDdpgApply, the pool commit CassieDdpgPoolCommit.  The noise eps is a
+ * float32 tensor [batch][act_dim] indexed by the position in the batch; the temperature is passed as a device pointer to log_alpha [1]. */
+
+/* parameters of the actor; 0 for an unsupported shape */
+int CassieSacParamCount(int obs_dim, int act_dim);
+
+/* One policy step for n environments in one launch: obs float64 [n][obs_dim] -> pool_obs_row [n][obs_dim] = its float32 image;
+ * pool_act_row [n][act_dim] = tanh(mean(obs) + exp(log_std(obs)) noise);  env_actions float64 = clip(low + (act + 1) / 2 (high - low), low, high).
+ * actor: host array of the six device pointers.  pool_obs_row / pool_act_row point at row `top` of the pool: the caller guarantees top + n <= capacity. */
+int CassieSacPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* const* actor, const float* noise_dev, const double* low_dev,
+                        const double* high_dev, float* pool_obs_row_dev, float* pool_act_row_dev, double* env_actions_dev, void* stream);
+
+/* Both critics' gradients on the batch idx [batch] in one launch: a' = pi(s'; eps_next),
+ *   y = rew + (1 - term) discount (min(Q1', Q2')(s', a') - exp(log_alpha) log pi(a'|s')),  e_k = Q_k(s, a) - y;
+ * partial [2][CassieDdpgPartialRows(batch)][CassieDdpgParamCount(critic) + 2]: block k is critic k's gradient of SUM e_k^2 in the order
+ * [gW1 | gb1 | gW2 | gb2 | gW3 | gb3], then sum e_k^2 and sum Q_k(s, a) -- the rows CassieDdpgApply(.., CASSIE_DDPG_CRITIC, ..) takes. */
+int CassieSacCriticGrad(const float* pool_obs, const float* pool_act, const float* pool_rew, const float* pool_term, const float* pool_next_obs,
+                        long long pool_capacity, const long long* idx_dev, int batch, int obs_dim, int act_dim, const float* const* actor,
+                        const float* const* target_qf1, const float* const* target_qf2, const float* const* qf1, const float* const* qf2,
+                        const float* eps_next_dev, const float* log_alpha_dev, float discount, float* partial_dev, void* stream);
+
+/* Actor gradient on the same batch: a~ = pi(s; eps); partial [rows][CassieSacParamCount + 2]: gradient of SUM (exp(log_alpha) log pi(a~|s) -
+ * min(Q1, Q2)(s, a~)) with respect to the actor through the critics as they are NOW (call it after their CassieDdpgApply), then sum log pi and
+ * sum min Q.  The clamp of log_std passes no gradient where it is active. */
+int CassieSacActorGrad(const float* pool_obs, long long pool_capacity, const long long* idx_dev, int batch, int obs_dim, int act_dim, const float* const* actor,
+                       const float* const* qf1, const float* const* qf2, const float* eps_dev, const float* log_alpha_dev, float* partial_dev, void* stream);
+
+/* One launch, one workgroup: g = scale * (the `rows` partial rows added in order);  Lasagne's Adam on the actor (t = the step count after its
+ * increment; there is no target actor);  log_alpha's Adam step (alpha_t likewise, its own m / v [1]) on the gradient
+ * -(scale * summed log pi column + target_entropy), alpha_m_dev == NULL: the temperature stays fixed;  stats_dev[0 .. 2] += (sum log pi,
+ * sum min Q, exp(log_alpha) sum log pi - sum min Q with log_alpha as it is before its step) (float64; NULL: not recorded). */
+int CassieSacApply(int rows, int obs_dim, int act_dim, const float* partial_dev, float scale, float* const* actor, float* m_dev, float* v_dev, int t, float lr,
+                   float beta1, float beta2, float eps, float* log_alpha_dev, float* alpha_m_dev, float* alpha_v_dev, int alpha_t, float alpha_lr,
+                   float target_entropy, double* stats_dev, void* stream);
+
 /* ---- PPO (cassierl_amd/ppo.py, csrc/tu_ppo.hip): GAE(lambda) advantages and the gradient of the clipped surrogate on a minibatch. */
 
 /* CassieTrpoReturnsAdvantages with GAE(lambda): backwards over the T steps of an environment's column, live = !cut[s],

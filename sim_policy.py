@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Counterpart of rllab/envs/sim_policy.py:19-31 on the batched MI355X environment: load a snapshot written by train_trpo.py,
-train_vpg.py or train_ddpg.py (`--snapshot`, snapshot_mode="last"; a VPG snapshot carries its policy's hidden sizes, a DDPG snapshot is rolled out with mu(s)) and roll the policy out -- no training.  The reference animates ONE env through rllab's
+train_vpg.py, train_ddpg.py or train_sac.py (`--snapshot`, snapshot_mode="last"; a VPG snapshot carries its policy's hidden sizes, a DDPG snapshot is rolled out with mu(s), a SAC snapshot with tanh of the Gaussian's mean or sample) and roll the policy out -- no training.  The reference animates ONE env through rllab's
 `rollout(env, policy, max_path_length, animated=True)`; here N resident envs run the same loop in parallel (there is no
 viewer: GUI is out of scope) and the script prints what the reference's loop would let one read off the screen: path
 lengths and returns.
@@ -50,9 +50,14 @@ def main():
         algo = make_cassie_ddpg(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
                                 terrain=terrain, replay_pool_size=args.envs)
         args.deterministic = True
+    elif ck.get("algo") == "sac":   # a train_sac.py snapshot: the squashed Gaussian; only the actor is loaded, so the smallest pool will do
+        from cassierl_amd.sac import make_cassie_sac
+        algo = make_cassie_sac(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
+                               terrain=terrain, replay_pool_size=args.envs)
     else:   # a train_trpo.py snapshot: 32 x 32 unless it records other hidden sizes
         algo = make_cassie_trpo(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
                                 terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (32, 32))))
+    squashed = ck.get("algo") == "sac"   # the action is tanh of the Gaussian's mean (--deterministic) or sample
     del ck
     _, _ = algo.load(args.file, restore_sampler=False)   # policy + baseline only: every path starts from env.reset()
     pol, n = algo.policy, args.envs
@@ -65,6 +70,8 @@ def main():
         for t in range(args.max_path_length):     # rllab.sampler.utils.rollout: until done or max_path_length
             mean, log_std = (pol(obs.to(dt)), None) if args.deterministic and not hasattr(pol, "dist_info") else pol.dist_info(obs.to(dt))
             a = mean if args.deterministic else mean + R.counter_normal(args.seed, algo.env_ids, t, mean.shape[1]).to(dt) * log_std.exp()
+            if squashed:
+                a = torch.tanh(a)
             obs, rew, done = algo.env_step(algo.act_map(a))
             ret += torch.where(alive, rew, torch.zeros_like(rew))
             length += alive.to(torch.int64)
