@@ -14,10 +14,11 @@ from test_gpu_ddpg import _free_port, _run, _small
 pytestmark = pytest.mark.gpu
 
 
-def _nets(D, A, seed):
+def _nets(D, A, seed, ls_width=0.05, ls_bias=-1.0, mean_bias=None):
     """Actor, two critics and their targets with test_gpu_ddpg._nets' scaling (HeUniform hidden weights, biases N(0, 0.1), output weights +-0.3, the
     critics' output bias 0.5); the actor's log_std head is scaled down (weights +-0.05, bias -1) so that it stays away from the clamp's bounds and
-    |u| stays moderate; the targets are other draws."""
+    |u| stays moderate; the targets are other draws.  ls_width, ls_bias: another log_std head (tests/test_gpu_offpolicy_edges.py: one that crosses the
+    clamp's bounds); mean_bias [A]: replaces the mean head's bias after every draw, so that the other parameters are those of the default."""
     import torch
     from cassierl_amd import ddpg as G
     from cassierl_amd import sac as S
@@ -31,14 +32,17 @@ def _nets(D, A, seed):
             net.l3.weight.uniform_(-0.3, 0.3)
         for qf in qfs:
             qf.l3.bias.fill_(0.5)
-        pol.l3.weight[A:].uniform_(-0.05, 0.05)
-        pol.l3.bias[A:].fill_(-1.0)
+        pol.l3.weight[A:].uniform_(-ls_width, ls_width)
+        pol.l3.bias[A:].fill_(ls_bias)
+        if mean_bias is not None:
+            pol.l3.bias[:A].copy_(torch.as_tensor(mean_bias, dtype=torch.float32))
     return [pol.cuda()] + [q.cuda() for q in qfs]   # actor, qf1, qf2, target_qf1, target_qf2
 
 
-def _margin_ok(pol, qf1, qf2, obs, act, noise, eps=1e-4):
+def _margin_ok(pol, qf1, qf2, obs, act, noise, eps=1e-4, inside=True, untied=True):
     """Rows (float64 reference) whose gradient-carrying hidden pre-activations all keep |z| >= eps (the actor at s, each live critic at (s, a) and at
-    (s, a~)), whose two critics are not tied at (s, a~), and whose log_std keeps eps from both bounds of the clamp."""
+    (s, a~)), whose two critics are not tied at (s, a~), and whose log_std keeps eps from both bounds of the clamp and lies between them.
+    inside=False keeps the rows whose raw log_std lies outside the bounds (still eps away from them); untied=False keeps the ties."""
     import torch
     p, q1, q2 = (copy.deepcopy(m).double() for m in (pol, qf1, qf2))
     o, a, e = obs.double(), act.double(), noise.double()
@@ -46,8 +50,8 @@ def _margin_ok(pol, qf1, qf2, obs, act, noise, eps=1e-4):
     with torch.no_grad():
         z1 = p.l1(o); z2 = p.l2(z1.relu())
         out = p.l3(z2.relu())
-        ls = out[:, A:]
-        at = torch.tanh(out[:, :A] + ls.exp() * e)
+        ls = out[:, A:]   # the raw head: where inside is required, the clamp changes nothing on the rows that are kept
+        at = torch.tanh(out[:, :A] + ls.clamp(-20.0, 2.0).exp() * e)
         conds, qs = [z1, z2], []
         for q in (q1, q2):
             y1 = q.l1(o)
@@ -55,12 +59,15 @@ def _margin_ok(pol, qf1, qf2, obs, act, noise, eps=1e-4):
             conds += [y1, y2, y2m]
             qs.append(q.l3(y2m.relu()).squeeze(-1))
         ok = torch.stack([(z.abs() >= eps).all(1) for z in conds]).all(0)
-        ok &= (qs[0] - qs[1]).abs() >= eps
-        ok &= ((ls - 2.0).abs() >= eps).all(1) & ((ls + 20.0).abs() >= eps).all(1) & (ls < 2.0).all(1) & (ls > -20.0).all(1)
+        if untied:
+            ok &= (qs[0] - qs[1]).abs() >= eps
+        ok &= ((ls - 2.0).abs() >= eps).all(1) & ((ls + 20.0).abs() >= eps).all(1)
+        if inside:
+            ok &= (ls < 2.0).all(1) & (ls > -20.0).all(1)
         return ok
 
 
-def _pool_with_margin(pol, qf1, qf2, D, A, candidates=40000, seed=11):
+def _pool_with_margin(pol, qf1, qf2, D, A, candidates=40000, seed=11, inside=True, untied=True):
     """test_gpu_ddpg._pool_with_margin with SAC's conditions.  The actor's noise belongs to the batch position, not to the pool row, so a row is
     kept only if it meets the conditions with the noise it will meet: the test draws batch position b's noise as noise_of_row[idx[b]]."""
     import torch
@@ -69,7 +76,7 @@ def _pool_with_margin(pol, qf1, qf2, D, A, candidates=40000, seed=11):
     obs = 0.7 * torch.randn(candidates, D, device="cuda", generator=g)
     act = torch.rand(candidates, A, device="cuda", generator=g) * 2 - 1
     noise = torch.randn(candidates, A, device="cuda", generator=g)
-    keep = _margin_ok(pol, qf1, qf2, obs, act, noise)
+    keep = _margin_ok(pol, qf1, qf2, obs, act, noise, inside=inside, untied=untied)
     dropped = 1.0 - keep.float().mean().item()
     obs, act, noise = obs[keep], act[keep], noise[keep]
     m = obs.shape[0]
