@@ -37,6 +37,8 @@ EXPORTS = [
     "CassieDdpgParamCount", "CassieDdpgPartialRows", "CassieDdpgPolicyStep", "CassieDdpgPoolCommit", "CassieDdpgCriticGrad", "CassieDdpgActorGrad", "CassieDdpgApply",
     # SAC (include/cassie_trpo.h)
     "CassieSacParamCount", "CassieSacPolicyStep", "CassieSacCriticGrad", "CassieSacActorGrad", "CassieSacApply",
+    # TD3 (include/cassie_trpo.h)
+    "CassieTd3PolicyStep", "CassieTd3CriticGrad", "CassieTd3CriticApply",
     # PPO (include/cassie_trpo.h)
     "CassieTrpoGae", "CassieTrpoClipGradRows", "CassieTrpoClipGrad", "CassiePgClipGradRows", "CassiePgClipGrad",
 ]

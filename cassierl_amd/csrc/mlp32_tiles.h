@@ -1,6 +1,7 @@
-// mlp32_tiles.h -- what the kernels of the 32 x 32 ReLU networks share (tu_ddpg.hip, tu_sac.hip): the shapes of a parameter row, the
+// mlp32_tiles.h -- what the kernels of the 32 x 32 ReLU networks share (tu_ddpg.hip, tu_sac.hip, tu_td3.hip): the shapes of a parameter row, the
 // A-operand images of every matrix product (laid out once per workgroup in LDS), the accumulator-layout helpers, the per-wavefront LDS
-// transposes and the fixed-order reduction of the wavefronts' rows.  The layout is tu_trpo.hip's (read its header first): exact float32
+// transposes, the fixed-order reduction of the wavefronts' rows, the live critic's tile pass of the twin-critic kernels and the Adam / soft-update
+// body of the apply kernels.  The layout is tu_trpo.hip's (read its header first): exact float32
 // v_mfma_f32_32x32x2_f32, a tile of 32 samples per wavefront, sample on the lane c = lane & 31, hidden unit r(v, h) = (v & 3) + 8 (v >> 2) + 4 h
 // in register v of the lane half h.
 #pragma once
@@ -152,6 +153,122 @@ __device__ __forceinline__ float q_head(const float (&w3)[16], float b3, const v
 // the wavefronts' rows of partial sums -> one row per workgroup, added in the order wave 0, 1, 2, 3
 template <int NROW> __device__ __forceinline__ void reduce_rows(const float* red, float* __restrict__ out) {
   for (int i = threadIdx.x; i < NROW; i += 64 * WAVES) out[i] = ((red[i] + red[NROW + i]) + red[2 * NROW + i]) + red[3 * NROW + i];
+}
+
+// ---- the live critic on a tile and its row of partial sums (tu_sac.hip, tu_td3.hip: both critics of a twin pair run through these)
+struct CriticAcc { v16f gW1, gW2, gW2a; float gW3[16]; float gb2, gb3, sse, sq; };
+__device__ __forceinline__ void zero(CriticAcc& a) {
+#pragma unroll
+  for (int v = 0; v < 16; v++) { a.gW1[v] = 0.0f; a.gW2[v] = 0.0f; a.gW2a[v] = 0.0f; a.gW3[v] = 0.0f; }
+  a.gb2 = a.gb3 = a.sse = a.sq = 0.0f;
+}
+// tu_ddpg.hip's critic_grad_kernel from "live critic at (s, a)" on, for the critic whose images start at q0 (W1 4, W2 4, action 1, W2' 4)
+enum { LQ_W1 = 0, LQ_W2 = 4, LQ_A = 8, LQ_W2T = 9, LQ_N = 13 };
+template <int KS1>
+__device__ __forceinline__ void critic_step(const float4 (*wimg)[64], int q0, const float* sb1, const float* sb2, const float* sw3, float b3, const float (&xb)[KS1],
+                                            const float (&ab)[4], const float (&xt)[16], const float (&at)[16], float y, bool valid, int lane, int c, int h,
+                                            float* t0, float* t1, CriticAcc& acc) {
+  v16f c1, c2;
+  two_layers<KS1>(wimg, q0 + LQ_W1, q0 + LQ_W2, sb1, sb2, xb, lane, h, c1, c2);
+  add_action(wimg, q0 + LQ_A, lane, ab, c2);
+  relu16(c2);
+  const v16f w3 = bias_tile(sw3, h);   // W3[r(v, h)] in register v
+  float w3a[16];
+#pragma unroll
+  for (int v = 0; v < 16; v++) w3a[v] = w3[v];
+  const float qv = q_head(w3a, b3, c2);
+  const float e = valid ? qv - y : 0.0f, dq = 2.0f * e;
+  if (h == 0 && valid) { acc.sse += e * e; acc.sq += qv; acc.gb3 += dq; }
+  v16f g2, g1;
+#pragma unroll
+  for (int v = 0; v < 16; v++) {
+    acc.gW3[v] = __builtin_fmaf(dq, c2[v], acc.gW3[v]);
+    g2[v] = c2[v] > 0.0f ? w3a[v] * dq : 0.0f;
+    g1[v] = 0.0f;
+  }
+  float aw[16], ta_[16], tb_[16];
+  aop(wimg, q0 + LQ_W2T, lane, aw);
+#pragma unroll
+  for (int v = 0; v < 16; v++) g1 = DDPG_MFMA(aw[v], g2[v], g1);
+#pragma unroll
+  for (int v = 0; v < 16; v++) g1[v] = c1[v] > 0.0f ? g1[v] : 0.0f;
+  put(t0, g2, c, h); put(t1, c1, c, h);
+  wave_lds_sync();
+  get(t0, ta_, c, h); get(t1, tb_, c, h);
+  wave_lds_sync();
+#pragma unroll
+  for (int s = 0; s < 16; s++) { acc.gW2 = DDPG_MFMA(ta_[s], tb_[s], acc.gW2); acc.gW2a = DDPG_MFMA(ta_[s], at[s], acc.gW2a); acc.gb2 += ta_[s]; }
+  put(t0, g1, c, h);
+  wave_lds_sync();
+  get(t0, ta_, c, h);
+  wave_lds_sync();
+#pragma unroll
+  for (int s = 0; s < 16; s++) acc.gW1 = DDPG_MFMA(ta_[s], xt[s], acc.gW1);
+}
+// this wavefront's row of a critic into LDS (tu_ddpg.hip's order)
+template <int D, int A> __device__ __forceinline__ void critic_row(CriticAcc& a, float* red, int lane, int c, int h) {
+  typedef Shape<D, A> S;
+#pragma unroll
+  for (int v = 0; v < 16; v++) {
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) a.gW3[v] += __shfl_xor(a.gW3[v], m, 64);   // over the 32 samples of the lane half
+  }
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) { a.sse += __shfl_xor(a.sse, m, 64); a.sq += __shfl_xor(a.sq, m, 64); a.gb3 += __shfl_xor(a.gb3, m, 64); }
+  a.gb2 += __shfl_xor(a.gb2, 32, 64);
+#pragma unroll
+  for (int v = 0; v < 16; v++) {
+    const int r = row_of(v, h);
+    red[S::Q_W2 + r * S::HA + c] = a.gW2[v];
+    if (c < A) red[S::Q_W2 + r * S::HA + H + c] = a.gW2a[v];
+    if (c < D) red[S::Q_W1 + r * D + c] = a.gW1[v];
+    if (c == D) red[S::Q_B1 + r] = a.gW1[v];
+    if (c == 0) red[S::Q_W3 + r] = a.gW3[v];
+  }
+  if (h == 0) red[S::Q_B2 + c] = a.gb2;
+  if (lane == 0) { red[S::Q_B3] = a.gb3; red[S::NPQ] = a.sse; red[S::NPQ + 1] = a.sq; }
+}
+
+// ---- Adam step and soft target update on a row of partial sums (tu_ddpg.hip's apply_kernel, tu_td3.hip's critic_apply_kernel): one workgroup of
+// 1024 threads.  g = scale * (rows of partial added in order);  Lasagne's Adam on the live network (tu_pg.hip: pg_adam_kernel);  target <- (1 - tau)
+// target + tau live;  stats[k] += the row sums of the `ns` columns behind the gradient (float64).  off: the starts of W1, b1, W2, b2, W3, b3 in the
+// row, and the parameter count.
+__device__ __forceinline__ void apply_rows(int rows, int ns, const float* partial, float scale, NetRW live, NetRW targ, const int (&off)[7], float* m, float* v, float a,
+                                           float beta1, float beta2, float eps, float tau, double* stats) {
+  const int np = off[6], stride = np + ns;
+  for (int i = threadIdx.x; i < np; i += 1024) {
+    float g = 0.0f;
+    const float* p = partial + i;
+    int r = 0;
+    for (; r + 8 <= rows; r += 8) {   // eight loads in flight, added in row order
+      float x[8];
+#pragma unroll
+      for (int k = 0; k < 8; k++) x[k] = p[(size_t)(r + k) * stride];
+#pragma unroll
+      for (int k = 0; k < 8; k++) g += x[k];
+    }
+    for (; r < rows; r++) g += p[(size_t)r * stride];
+    g *= scale;
+    float *th, *tg;
+    int j;
+    if (i < off[1]) { th = live.W1; tg = targ.W1; j = i - off[0]; }
+    else if (i < off[2]) { th = live.b1; tg = targ.b1; j = i - off[1]; }
+    else if (i < off[3]) { th = live.W2; tg = targ.W2; j = i - off[2]; }
+    else if (i < off[4]) { th = live.b2; tg = targ.b2; j = i - off[3]; }
+    else if (i < off[5]) { th = live.W3; tg = targ.W3; j = i - off[4]; }
+    else { th = live.b3; tg = targ.b3; j = i - off[5]; }
+    const float mi = beta1 * m[i] + (1.0f - beta1) * g;
+    const float vi = beta2 * v[i] + (1.0f - beta2) * (g * g);
+    m[i] = mi; v[i] = vi;
+    const float t = th[j] - a * mi / (sqrtf(vi) + eps);
+    th[j] = t;
+    tg[j] = (1.0f - tau) * tg[j] + tau * t;
+  }
+  if ((int)threadIdx.x < ns && stats) {
+    double s = 0.0;
+    for (int r = 0; r < rows; r++) s += (double)partial[(size_t)r * stride + np + threadIdx.x];
+    stats[threadIdx.x] += s;
+  }
 }
 
 inline int blocks_for(int n) {

@@ -315,40 +315,7 @@ struct Offsets { int o[7]; };   // starts of W1, b1, W2, b2, W3, b3 in the row, 
 __global__ void __launch_bounds__(1024) apply_kernel(int rows, int ns, const float* __restrict__ partial, float scale, NetRW live, NetRW targ, Offsets off,
                                                      float* __restrict__ m, float* __restrict__ v, float a, float beta1, float beta2, float eps, float tau,
                                                      double* __restrict__ stats) {
-  const int np = off.o[6], stride = np + ns;
-  for (int i = threadIdx.x; i < np; i += 1024) {
-    float g = 0.0f;
-    const float* p = partial + i;
-    int r = 0;
-    for (; r + 8 <= rows; r += 8) {   // eight loads in flight, added in row order
-      float x[8];
-#pragma unroll
-      for (int k = 0; k < 8; k++) x[k] = p[(size_t)(r + k) * stride];
-#pragma unroll
-      for (int k = 0; k < 8; k++) g += x[k];
-    }
-    for (; r < rows; r++) g += p[(size_t)r * stride];
-    g *= scale;
-    float *th, *tg;
-    int j;
-    if (i < off.o[1]) { th = live.W1; tg = targ.W1; j = i - off.o[0]; }
-    else if (i < off.o[2]) { th = live.b1; tg = targ.b1; j = i - off.o[1]; }
-    else if (i < off.o[3]) { th = live.W2; tg = targ.W2; j = i - off.o[2]; }
-    else if (i < off.o[4]) { th = live.b2; tg = targ.b2; j = i - off.o[3]; }
-    else if (i < off.o[5]) { th = live.W3; tg = targ.W3; j = i - off.o[4]; }
-    else { th = live.b3; tg = targ.b3; j = i - off.o[5]; }
-    const float mi = beta1 * m[i] + (1.0f - beta1) * g;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * (g * g);
-    m[i] = mi; v[i] = vi;
-    const float t = th[j] - a * mi / (sqrtf(vi) + eps);
-    th[j] = t;
-    tg[j] = (1.0f - tau) * tg[j] + tau * t;
-  }
-  if ((int)threadIdx.x < ns && stats) {
-    double s = 0.0;
-    for (int r = 0; r < rows; r++) s += (double)partial[(size_t)r * stride + np + threadIdx.x];
-    stats[threadIdx.x] += s;
-  }
+  apply_rows(rows, ns, partial, scale, live, targ, off.o, m, v, a, beta1, beta2, eps, tau, stats);   // mlp32_tiles.h
 }
 
 // ---------------------------------------------------------------------------------------------------------------- policy step

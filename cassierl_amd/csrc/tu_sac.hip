@@ -74,79 +74,7 @@ __device__ __forceinline__ void actor_sample(const float4 (*wimg)[64], int qW1, 
 // Per sample b (pool row i = idx[b]):  a' = pi(s'_i; eps[b]),  y = r_i + (1 - terminal_i) gamma (min(Q1', Q2')(s'_i, a') - alpha log pi(a'|s'_i)),
 // e_k = Q_k(s_i, a_i) - y, and the gradient of sum_b e_k^2 with respect to live critic k.  Block k of partial: [rows][gW1 | gb1 | gW2 | gb2 |
 // gW3 | gb3 | sum e_k^2 | sum Q_k].
-struct CriticAcc { v16f gW1, gW2, gW2a; float gW3[16]; float gb2, gb3, sse, sq; };
-__device__ __forceinline__ void zero(CriticAcc& a) {
-#pragma unroll
-  for (int v = 0; v < 16; v++) { a.gW1[v] = 0.0f; a.gW2[v] = 0.0f; a.gW2a[v] = 0.0f; a.gW3[v] = 0.0f; }
-  a.gb2 = a.gb3 = a.sse = a.sq = 0.0f;
-}
-// tu_ddpg.hip's critic_grad_kernel from "live critic at (s, a)" on, for the critic whose images start at q0 (W1 4, W2 4, action 1, W2' 4)
-enum { LQ_W1 = 0, LQ_W2 = 4, LQ_A = 8, LQ_W2T = 9, LQ_N = 13 };
-template <int KS1>
-__device__ __forceinline__ void critic_step(const float4 (*wimg)[64], int q0, const float* sb1, const float* sb2, const float* sw3, float b3, const float (&xb)[KS1],
-                                            const float (&ab)[4], const float (&xt)[16], const float (&at)[16], float y, bool valid, int lane, int c, int h,
-                                            float* t0, float* t1, CriticAcc& acc) {
-  v16f c1, c2;
-  two_layers<KS1>(wimg, q0 + LQ_W1, q0 + LQ_W2, sb1, sb2, xb, lane, h, c1, c2);
-  add_action(wimg, q0 + LQ_A, lane, ab, c2);
-  relu16(c2);
-  const v16f w3 = bias_tile(sw3, h);   // W3[r(v, h)] in register v
-  float w3a[16];
-#pragma unroll
-  for (int v = 0; v < 16; v++) w3a[v] = w3[v];
-  const float qv = q_head(w3a, b3, c2);
-  const float e = valid ? qv - y : 0.0f, dq = 2.0f * e;
-  if (h == 0 && valid) { acc.sse += e * e; acc.sq += qv; acc.gb3 += dq; }
-  v16f g2, g1;
-#pragma unroll
-  for (int v = 0; v < 16; v++) {
-    acc.gW3[v] = __builtin_fmaf(dq, c2[v], acc.gW3[v]);
-    g2[v] = c2[v] > 0.0f ? w3a[v] * dq : 0.0f;
-    g1[v] = 0.0f;
-  }
-  float aw[16], ta_[16], tb_[16];
-  aop(wimg, q0 + LQ_W2T, lane, aw);
-#pragma unroll
-  for (int v = 0; v < 16; v++) g1 = DDPG_MFMA(aw[v], g2[v], g1);
-#pragma unroll
-  for (int v = 0; v < 16; v++) g1[v] = c1[v] > 0.0f ? g1[v] : 0.0f;
-  put(t0, g2, c, h); put(t1, c1, c, h);
-  wave_lds_sync();
-  get(t0, ta_, c, h); get(t1, tb_, c, h);
-  wave_lds_sync();
-#pragma unroll
-  for (int s = 0; s < 16; s++) { acc.gW2 = DDPG_MFMA(ta_[s], tb_[s], acc.gW2); acc.gW2a = DDPG_MFMA(ta_[s], at[s], acc.gW2a); acc.gb2 += ta_[s]; }
-  put(t0, g1, c, h);
-  wave_lds_sync();
-  get(t0, ta_, c, h);
-  wave_lds_sync();
-#pragma unroll
-  for (int s = 0; s < 16; s++) acc.gW1 = DDPG_MFMA(ta_[s], xt[s], acc.gW1);
-}
-// this wavefront's row of a critic into LDS (tu_ddpg.hip's order)
-template <int D, int A> __device__ __forceinline__ void critic_row(CriticAcc& a, float* red, int lane, int c, int h) {
-  typedef Shape<D, A> S;
-#pragma unroll
-  for (int v = 0; v < 16; v++) {
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) a.gW3[v] += __shfl_xor(a.gW3[v], m, 64);   // over the 32 samples of the lane half
-  }
-#pragma unroll
-  for (int m = 16; m >= 1; m >>= 1) { a.sse += __shfl_xor(a.sse, m, 64); a.sq += __shfl_xor(a.sq, m, 64); a.gb3 += __shfl_xor(a.gb3, m, 64); }
-  a.gb2 += __shfl_xor(a.gb2, 32, 64);
-#pragma unroll
-  for (int v = 0; v < 16; v++) {
-    const int r = row_of(v, h);
-    red[S::Q_W2 + r * S::HA + c] = a.gW2[v];
-    if (c < A) red[S::Q_W2 + r * S::HA + H + c] = a.gW2a[v];
-    if (c < D) red[S::Q_W1 + r * D + c] = a.gW1[v];
-    if (c == D) red[S::Q_B1 + r] = a.gW1[v];
-    if (c == 0) red[S::Q_W3 + r] = a.gW3[v];
-  }
-  if (h == 0) red[S::Q_B2 + c] = a.gb2;
-  if (lane == 0) { red[S::Q_B3] = a.gb3; red[S::NPQ] = a.sse; red[S::NPQ + 1] = a.sq; }
-}
-
+// CriticAcc, critic_step and critic_row (the live critic's forward and reverse pass on a tile, its row of partial sums) are mlp32_tiles.h's.
 enum { CQ_PI_W1 = 0, CQ_PI_W2 = 4, CQ_PI_W3 = 8, CQ_T1_W1 = 12, CQ_T1_W2 = 16, CQ_T1_A = 20, CQ_T2_W1 = 21, CQ_T2_W2 = 25, CQ_T2_A = 29, CQ_Q1 = 30, CQ_Q2 = CQ_Q1 + LQ_N,
        CQ_N = CQ_Q2 + LQ_N };
 template <int D, int A>

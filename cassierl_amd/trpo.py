@@ -953,7 +953,7 @@ class TRPO:
     def _load_fields(self, ck):
         """Called with the loaded snapshot before anything is restored: refuses a snapshot that is not this run's (a subclass also takes
         back its _snapshot_fields()).  TRPO: the policy's hidden sizes must match (a snapshot without them was written by a 32 x 32 run)."""
-        if ck.get("algo") in ("ddpg", "sac"):   # their "policy" is a deterministic / squashed-Gaussian actor, not a GaussianMLPPolicy
+        if ck.get("algo") in ("ddpg", "sac", "td3"):   # their "policy" is a deterministic / squashed-Gaussian actor, not a GaussianMLPPolicy
             raise ValueError("TRPO.load: the snapshot was written by %s, this run is trpo" % ck["algo"])
         theirs, mine = tuple(ck.get("hidden_sizes", (32, 32))), hidden_sizes_of(self.policy)
         if theirs != mine:

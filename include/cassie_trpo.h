@@ -232,6 +232,36 @@ int CassieSacApply(int rows, int obs_dim, int act_dim, const float* partial_dev,
                    float beta1, float beta2, float eps, float* log_alpha_dev, float* alpha_m_dev, float* alpha_v_dev, int alpha_t, float alpha_lr,
                    float target_entropy, double* stats_dev, void* stream);
 
+/* ---- TD3 (cassierl_amd/td3.py, csrc/tu_td3.hip): DDPG's actor, two of DDPG's critics, a target of each, DDPG's shapes and replay pool.  The
+ * critics' parameter count is CassieDdpgParamCount(.., CASSIE_DDPG_CRITIC), the rows of partial sums of a batch CassieDdpgPartialRows(batch), the pool
+ * commit CassieDdpgPoolCommit.  The delayed actor step is CassieDdpgActorGrad with qf1 as the critic and CassieDdpgApply(.., CASSIE_DDPG_ACTOR, ..). */
+
+/* One policy step for n environments in one launch: obs float64 [n][obs_dim] -> pool_obs_row [n][obs_dim] = its float32 image;
+ * pool_act_row [n][act_dim] = clip(mu(obs) + sigma noise, -1, 1);  env_actions float64 = clip(low + (act + 1) / 2 (high - low), low, high).
+ * actor: host array of the six device pointers.  pool_obs_row / pool_act_row point at row `top` of the pool: the caller guarantees top + n <= capacity.
+ * obs_dim 26 only. */
+int CassieTd3PolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* const* actor, const float* noise_dev, float sigma, const double* low_dev,
+                        const double* high_dev, float* pool_obs_row_dev, float* pool_act_row_dev, double* env_actions_dev, void* stream);
+
+/* Both critics' gradients on the batch idx [batch] (int64 pool rows, clamped to [0, pool_capacity)) in one launch:
+ *   a' = clip(mu'(s') + clip(policy_noise eps_next, -noise_clip, noise_clip), -1, 1),  y = rew + (1 - term) discount min(Q1', Q2')(s', a'),
+ *   e_k = Q_k(s, a) - y;
+ * eps_next float32 [batch][act_dim], indexed by the position in the batch; noise_clip >= 0; policy_noise = 0 gives the unsmoothed target.
+ * partial [2][CassieDdpgPartialRows(batch)][CassieDdpgParamCount(critic) + 2]: block k is critic k's gradient of SUM e_k^2 in the order
+ * [gW1 | gb1 | gW2 | gb2 | gW3 | gb3], then sum e_k^2 and sum Q_k(s, a) -- CassieSacCriticGrad's layout. */
+int CassieTd3CriticGrad(const float* pool_obs, const float* pool_act, const float* pool_rew, const float* pool_term, const float* pool_next_obs,
+                        long long pool_capacity, const long long* idx_dev, int batch, int obs_dim, int act_dim, const float* const* target_actor,
+                        const float* const* target_qf1, const float* const* target_qf2, const float* const* qf1, const float* const* qf2,
+                        const float* eps_next_dev, float policy_noise, float noise_clip, float discount, float* partial_dev, void* stream);
+
+/* One launch, two workgroups: workgroup k does for critic k on block k of partial [2][rows][CassieDdpgParamCount(critic) + 2] what
+ * CassieDdpgApply(.., CASSIE_DDPG_CRITIC, ..) does, bit for bit (the `rows` rows added in order, Adam with t = the step count after its increment,
+ * target k <- (1 - tau) target k + tau critic k; tau = 0 leaves the target's bits);  stats_dev[0 .. 3] += (sum e_1^2, sum Q_1, sum e_2^2, sum Q_2)
+ * (float64; NULL: not recorded). */
+int CassieTd3CriticApply(int rows, int obs_dim, int act_dim, const float* partial_dev, float scale, float* const* qf1, float* const* qf2, float* const* target_qf1,
+                         float* const* target_qf2, float* m1_dev, float* v1_dev, float* m2_dev, float* v2_dev, int t, float lr, float beta1, float beta2, float eps,
+                         float tau, double* stats_dev, void* stream);
+
 /* ---- PPO (cassierl_amd/ppo.py, csrc/tu_ppo.hip): GAE(lambda) advantages and the gradient of the clipped surrogate on a minibatch. */
 
 /* CassieTrpoReturnsAdvantages with GAE(lambda): backwards over the T steps of an environment's column, live = !cut[s],

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Counterpart of rllab/envs/sim_policy.py:19-31 on the batched MI355X environment: load a snapshot written by train_trpo.py,
-train_vpg.py, train_ddpg.py or train_sac.py (`--snapshot`, snapshot_mode="last"; a VPG snapshot carries its policy's hidden sizes, a DDPG snapshot is rolled out with mu(s), a SAC snapshot with tanh of the Gaussian's mean or sample) and roll the policy out -- no training.  The reference animates ONE env through rllab's
+train_vpg.py, train_ddpg.py, train_sac.py or train_td3.py (`--snapshot`, snapshot_mode="last"; a VPG snapshot carries its policy's hidden sizes, a DDPG or TD3 snapshot is rolled out with mu(s), a SAC snapshot with tanh of the Gaussian's mean or sample) and roll the policy out -- no training.  The reference animates ONE env through rllab's
 `rollout(env, policy, max_path_length, animated=True)`; here N resident envs run the same loop in parallel (there is no
 viewer: GUI is out of scope) and the script prints what the reference's loop would let one read off the screen: path
 lengths and returns.
@@ -49,6 +49,11 @@ def main():
         from cassierl_amd.ddpg import make_cassie_ddpg
         algo = make_cassie_ddpg(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
                                 terrain=terrain, replay_pool_size=args.envs)
+        args.deterministic = True
+    elif ck.get("algo") == "td3":   # a train_td3.py snapshot: the deterministic actor mu(s), as for DDPG
+        from cassierl_amd.td3 import make_cassie_td3
+        algo = make_cassie_td3(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
+                               terrain=terrain, replay_pool_size=args.envs)
         args.deterministic = True
     elif ck.get("algo") == "sac":   # a train_sac.py snapshot: the squashed Gaussian; only the actor is loaded, so the smallest pool will do
         from cassierl_amd.sac import make_cassie_sac
