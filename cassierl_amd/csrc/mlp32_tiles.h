@@ -276,9 +276,35 @@ inline int blocks_for(int n) {
   const int b = (tiles + WAVES - 1) / WAVES;
   return b < 1 ? 1 : (b > MAX_BLOCKS ? MAX_BLOCKS : b);
 }
+inline int policy_step_grid(int n) { return ((n + 31) / 32 + WAVES - 1) / WAVES; }   // the policy-step kernels: one tile per wavefront
 inline bool shape_ok(int D, int A) { return (D == 26 || D == 17) && (A == 6 || A == 7); }
 inline bool net_ok(const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3) { return W1 && b1 && W2 && b2 && W3 && b3; }
+// a network as the C ABI passes it: a host array of the six device pointers {W1, b1, W2, b2, W3, b3}
+template <class P> inline bool net_ok(P p) { return p && net_ok(p[0], p[1], p[2], p[3], p[4], p[5]); }
+inline Net net_of(const float* const* p) { return Net{p[0], p[1], p[2], p[3], p[4], p[5]}; }
+inline NetRW net_rw(float* const* p) { return NetRW{p[0], p[1], p[2], p[3], p[4], p[5]}; }
 inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 inline bool pool_ok(const Pool& p) { return p.obs && p.act && p.rew && p.term && p.nobs && p.cap > 0; }
 
+// apply_rows' `off` for a row [W1 | b1 | W2 | b2 | W3 | b3]: an actor with rows_out output units (A, or 2 A with two heads), and the critic
+inline void row_offsets(int obs_dim, int w2_cols, int rows_out, int (&off)[7]) {
+  const int len[6] = {H * obs_dim, H, H * w2_cols, H, rows_out * H, rows_out};
+  off[0] = 0;
+  for (int k = 0; k < 6; k++) off[k + 1] = off[k] + len[k];
+}
+inline void actor_offsets(int obs_dim, int rows_out, int (&off)[7]) { row_offsets(obs_dim, H, rows_out, off); }
+inline void critic_offsets(int obs_dim, int act_dim, int (&off)[7]) { row_offsets(obs_dim, H + act_dim, 1, off); }
+// Lasagne's Adam: the step size of step t with both bias corrections folded in (float64 on the host, as tu_pg.hip)
+inline float adam_step_size(float lr, float beta1, float beta2, int t) { return (float)((double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t))); }
+
 }  // namespace cassie_mlp32
+
+// Launch KERNEL<D, A>(...) on `grid` workgroups of WAVES wavefronts for the (obs_dim, act_dim) the library is built for, in a function that
+// returns a CASSIE_* code: any other shape returns CASSIE_EINVAL from it.  MLP32_LAUNCH: the update kernels (D 26 or 17, A 6 or 7);
+// MLP32_LAUNCH_STEP: the policy-step kernels (the environment's 26-wide rows only).
+#define MLP32_CASE(KERNEL, D_, A_, obs_dim, act_dim, grid, stream, ...) \
+  if ((obs_dim) == D_ && (act_dim) == A_) hipLaunchKernelGGL((KERNEL<D_, A_>), dim3(grid), dim3(64 * cassie_mlp32::WAVES), 0, (hipStream_t)(stream), __VA_ARGS__); else
+#define MLP32_LAUNCH_STEP(KERNEL, ...) MLP32_CASE(KERNEL, 26, 6, __VA_ARGS__) MLP32_CASE(KERNEL, 26, 7, __VA_ARGS__) return CASSIE_EINVAL
+#define MLP32_LAUNCH(KERNEL, ...) \
+  MLP32_CASE(KERNEL, 26, 6, __VA_ARGS__) MLP32_CASE(KERNEL, 26, 7, __VA_ARGS__) MLP32_CASE(KERNEL, 17, 6, __VA_ARGS__) MLP32_CASE(KERNEL, 17, 7, __VA_ARGS__) \
+  return CASSIE_EINVAL

@@ -416,14 +416,8 @@ int CassieDdpgPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim,
       !pool_act_row_dev || !env_actions_dev)
     return CASSIE_EINVAL;
   const Net th{W1, b1, W2, b2, W3, b3};
-  const dim3 grid(((n + 31) / 32 + WAVES - 1) / WAVES), block(64 * WAVES);
-  hipStream_t s = (hipStream_t)stream;
-#define DDPG_STEP(D_, A_) hipLaunchKernelGGL((policy_step_kernel<D_, A_>), grid, block, 0, s, obs_dev, n, th, noise_dev, path_t_dev, ou_theta, ou_sigma, ou_mu, \
-                                             ou_state_dev, low_dev, high_dev, pool_obs_row_dev, pool_act_row_dev, env_actions_dev)
-  if (obs_dim == 26 && act_dim == 6) DDPG_STEP(26, 6);
-  else if (obs_dim == 26 && act_dim == 7) DDPG_STEP(26, 7);
-  else return CASSIE_EINVAL;
-#undef DDPG_STEP
+  MLP32_LAUNCH_STEP(policy_step_kernel, obs_dim, act_dim, policy_step_grid(n), stream, obs_dev, n, th, noise_dev, path_t_dev, ou_theta, ou_sigma, ou_mu, ou_state_dev,
+                    low_dev, high_dev, pool_obs_row_dev, pool_act_row_dev, env_actions_dev);
   return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
 }
 
@@ -442,58 +436,33 @@ int CassieDdpgCriticGrad(const float* pool_obs, const float* pool_act, const flo
                          void* stream) {
   using namespace cassie_ddpg;
   const Pool pool{pool_obs, pool_act, pool_rew, pool_term, pool_next_obs, pool_capacity};
-  if (!pool_ok(pool) || !idx_dev || batch <= 0 || !target_actor || !target_critic || !critic || !partial_dev || !aligned4(partial_dev)) return CASSIE_EINVAL;
-  const Net ta{target_actor[0], target_actor[1], target_actor[2], target_actor[3], target_actor[4], target_actor[5]};
-  const Net tq{target_critic[0], target_critic[1], target_critic[2], target_critic[3], target_critic[4], target_critic[5]};
-  const Net q{critic[0], critic[1], critic[2], critic[3], critic[4], critic[5]};
-  if (!net_ok(ta.W1, ta.b1, ta.W2, ta.b2, ta.W3, ta.b3) || !net_ok(tq.W1, tq.b1, tq.W2, tq.b2, tq.W3, tq.b3) || !net_ok(q.W1, q.b1, q.W2, q.b2, q.W3, q.b3))
-    return CASSIE_EINVAL;
-  const dim3 grid(blocks_for(batch)), block(64 * WAVES);
-  hipStream_t s = (hipStream_t)stream;
-#define DDPG_CQ(D_, A_) hipLaunchKernelGGL((critic_grad_kernel<D_, A_>), grid, block, 0, s, pool, idx_dev, batch, ta, tq, q, discount, partial_dev)
-  if (obs_dim == 26 && act_dim == 6) DDPG_CQ(26, 6);
-  else if (obs_dim == 26 && act_dim == 7) DDPG_CQ(26, 7);
-  else if (obs_dim == 17 && act_dim == 6) DDPG_CQ(17, 6);
-  else if (obs_dim == 17 && act_dim == 7) DDPG_CQ(17, 7);
-  else return CASSIE_EINVAL;
-#undef DDPG_CQ
+  if (!pool_ok(pool) || !idx_dev || batch <= 0 || !partial_dev || !aligned4(partial_dev)) return CASSIE_EINVAL;
+  if (!net_ok(target_actor) || !net_ok(target_critic) || !net_ok(critic)) return CASSIE_EINVAL;
+  MLP32_LAUNCH(critic_grad_kernel, obs_dim, act_dim, blocks_for(batch), stream, pool, idx_dev, batch, net_of(target_actor), net_of(target_critic), net_of(critic),
+               discount, partial_dev);
   return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
 }
 
 int CassieDdpgActorGrad(const float* pool_obs, long long pool_capacity, const long long* idx_dev, int batch, int obs_dim, int act_dim, const float* const* actor,
                         const float* const* critic, float* partial_dev, void* stream) {
   using namespace cassie_ddpg;
-  if (!pool_obs || pool_capacity <= 0 || !idx_dev || batch <= 0 || !actor || !critic || !partial_dev || !aligned4(partial_dev)) return CASSIE_EINVAL;
+  if (!pool_obs || pool_capacity <= 0 || !idx_dev || batch <= 0 || !net_ok(actor) || !net_ok(critic) || !partial_dev || !aligned4(partial_dev)) return CASSIE_EINVAL;
   const Pool pool{pool_obs, nullptr, nullptr, nullptr, nullptr, pool_capacity};
-  const Net th{actor[0], actor[1], actor[2], actor[3], actor[4], actor[5]};
-  const Net q{critic[0], critic[1], critic[2], critic[3], critic[4], critic[5]};
-  if (!net_ok(th.W1, th.b1, th.W2, th.b2, th.W3, th.b3) || !net_ok(q.W1, q.b1, q.W2, q.b2, q.W3, q.b3)) return CASSIE_EINVAL;
-  const dim3 grid(blocks_for(batch)), block(64 * WAVES);
-  hipStream_t s = (hipStream_t)stream;
-#define DDPG_AG(D_, A_) hipLaunchKernelGGL((actor_grad_kernel<D_, A_>), grid, block, 0, s, pool, idx_dev, batch, th, q, partial_dev)
-  if (obs_dim == 26 && act_dim == 6) DDPG_AG(26, 6);
-  else if (obs_dim == 26 && act_dim == 7) DDPG_AG(26, 7);
-  else if (obs_dim == 17 && act_dim == 6) DDPG_AG(17, 6);
-  else if (obs_dim == 17 && act_dim == 7) DDPG_AG(17, 7);
-  else return CASSIE_EINVAL;
-#undef DDPG_AG
+  MLP32_LAUNCH(actor_grad_kernel, obs_dim, act_dim, blocks_for(batch), stream, pool, idx_dev, batch, net_of(actor), net_of(critic), partial_dev);
   return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
 }
 
 int CassieDdpgApply(int rows, int obs_dim, int act_dim, int which, const float* partial_dev, float scale, float* const* live, float* const* target, float* m_dev,
                     float* v_dev, int t, float lr, float beta1, float beta2, float eps, float tau, double* stats_dev, void* stream) {
   using namespace cassie_ddpg;
-  const int np = CassieDdpgParamCount(obs_dim, act_dim, which);
-  if (np == 0 || rows <= 0 || !partial_dev || !live || !target || !m_dev || !v_dev || t < 1) return CASSIE_EINVAL;
-  const NetRW lv{live[0], live[1], live[2], live[3], live[4], live[5]}, tg{target[0], target[1], target[2], target[3], target[4], target[5]};
-  if (!net_ok(lv.W1, lv.b1, lv.W2, lv.b2, lv.W3, lv.b3) || !net_ok(tg.W1, tg.b1, tg.W2, tg.b2, tg.W3, tg.b3)) return CASSIE_EINVAL;
-  const int Hh = 32, w2 = which == CASSIE_DDPG_ACTOR ? Hh * Hh : Hh * (Hh + act_dim), w3 = which == CASSIE_DDPG_ACTOR ? act_dim * Hh : Hh;
+  const bool actor = which == CASSIE_DDPG_ACTOR;
+  if (CassieDdpgParamCount(obs_dim, act_dim, which) == 0 || rows <= 0 || !partial_dev || !net_ok(live) || !net_ok(target) || !m_dev || !v_dev || t < 1)
+    return CASSIE_EINVAL;
   Offsets off;
-  off.o[0] = 0; off.o[1] = Hh * obs_dim; off.o[2] = off.o[1] + Hh; off.o[3] = off.o[2] + w2; off.o[4] = off.o[3] + Hh; off.o[5] = off.o[4] + w3; off.o[6] = np;
-  const int ns = which == CASSIE_DDPG_ACTOR ? 1 : 2;
-  const double a = (double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t));
-  hipLaunchKernelGGL(apply_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, rows, ns, partial_dev, scale, lv, tg, off, m_dev, v_dev, (float)a, beta1, beta2, eps,
-                     tau, stats_dev);
+  if (actor) actor_offsets(obs_dim, act_dim, off.o);
+  else critic_offsets(obs_dim, act_dim, off.o);
+  hipLaunchKernelGGL(apply_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, rows, actor ? 1 : 2, partial_dev, scale, net_rw(live), net_rw(target), off, m_dev, v_dev,
+                     adam_step_size(lr, beta1, beta2, t), beta1, beta2, eps, tau, stats_dev);
   return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
 }
 

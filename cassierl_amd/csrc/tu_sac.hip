@@ -437,9 +437,6 @@ __global__ void __launch_bounds__(64 * WAVES, 2) policy_step_kernel(const double
   }
 }
 
-inline Net net_of(const float* const* p) { return Net{p[0], p[1], p[2], p[3], p[4], p[5]}; }
-inline bool net_ok(const float* const* p) { return p && cassie_mlp32::net_ok(p[0], p[1], p[2], p[3], p[4], p[5]); }
-
 }  // namespace cassie_sac
 
 extern "C" {
@@ -452,17 +449,9 @@ int CassieSacParamCount(int obs_dim, int act_dim) {
 int CassieSacPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* const* actor, const float* noise_dev, const double* low_dev,
                         const double* high_dev, float* pool_obs_row_dev, float* pool_act_row_dev, double* env_actions_dev, void* stream) {
   using namespace cassie_sac;
-  if (!obs_dev || n <= 0 || !cassie_sac::net_ok(actor) || !noise_dev || !low_dev || !high_dev || !pool_obs_row_dev || !pool_act_row_dev || !env_actions_dev)
-    return CASSIE_EINVAL;
-  const Net th = net_of(actor);
-  const dim3 grid(((n + 31) / 32 + WAVES - 1) / WAVES), block(64 * WAVES);
-  hipStream_t s = (hipStream_t)stream;
-#define SAC_STEP(D_, A_) hipLaunchKernelGGL((policy_step_kernel<D_, A_>), grid, block, 0, s, obs_dev, n, th, noise_dev, low_dev, high_dev, pool_obs_row_dev, \
-                                            pool_act_row_dev, env_actions_dev)
-  if (obs_dim == 26 && act_dim == 6) SAC_STEP(26, 6);
-  else if (obs_dim == 26 && act_dim == 7) SAC_STEP(26, 7);
-  else return CASSIE_EINVAL;
-#undef SAC_STEP
+  if (!obs_dev || n <= 0 || !net_ok(actor) || !noise_dev || !low_dev || !high_dev || !pool_obs_row_dev || !pool_act_row_dev || !env_actions_dev) return CASSIE_EINVAL;
+  MLP32_LAUNCH_STEP(policy_step_kernel, obs_dim, act_dim, policy_step_grid(n), stream, obs_dev, n, net_of(actor), noise_dev, low_dev, high_dev, pool_obs_row_dev,
+                    pool_act_row_dev, env_actions_dev);
   return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
 }
 
@@ -473,19 +462,9 @@ int CassieSacCriticGrad(const float* pool_obs, const float* pool_act, const floa
   using namespace cassie_sac;
   const Pool pool{pool_obs, pool_act, pool_rew, pool_term, pool_next_obs, pool_capacity};
   if (!pool_ok(pool) || !idx_dev || batch <= 0 || !eps_next_dev || !log_alpha_dev || !partial_dev || !aligned4(partial_dev)) return CASSIE_EINVAL;
-  if (!cassie_sac::net_ok(actor) || !cassie_sac::net_ok(target_qf1) || !cassie_sac::net_ok(target_qf2) || !cassie_sac::net_ok(qf1) || !cassie_sac::net_ok(qf2))
-    return CASSIE_EINVAL;
-  const Net pi = net_of(actor), t1 = net_of(target_qf1), t2 = net_of(target_qf2), q1 = net_of(qf1), q2 = net_of(qf2);
-  const dim3 grid(blocks_for(batch)), block(64 * WAVES);
-  hipStream_t s = (hipStream_t)stream;
-#define SAC_CQ(D_, A_) hipLaunchKernelGGL((critic_grad_kernel<D_, A_>), grid, block, 0, s, pool, idx_dev, batch, pi, t1, t2, q1, q2, eps_next_dev, log_alpha_dev, \
-                                          discount, partial_dev)
-  if (obs_dim == 26 && act_dim == 6) SAC_CQ(26, 6);
-  else if (obs_dim == 26 && act_dim == 7) SAC_CQ(26, 7);
-  else if (obs_dim == 17 && act_dim == 6) SAC_CQ(17, 6);
-  else if (obs_dim == 17 && act_dim == 7) SAC_CQ(17, 7);
-  else return CASSIE_EINVAL;
-#undef SAC_CQ
+  if (!net_ok(actor) || !net_ok(target_qf1) || !net_ok(target_qf2) || !net_ok(qf1) || !net_ok(qf2)) return CASSIE_EINVAL;
+  MLP32_LAUNCH(critic_grad_kernel, obs_dim, act_dim, blocks_for(batch), stream, pool, idx_dev, batch, net_of(actor), net_of(target_qf1), net_of(target_qf2), net_of(qf1),
+               net_of(qf2), eps_next_dev, log_alpha_dev, discount, partial_dev);
   return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
 }
 
@@ -493,18 +472,10 @@ int CassieSacActorGrad(const float* pool_obs, long long pool_capacity, const lon
                        const float* const* qf1, const float* const* qf2, const float* eps_dev, const float* log_alpha_dev, float* partial_dev, void* stream) {
   using namespace cassie_sac;
   if (!pool_obs || pool_capacity <= 0 || !idx_dev || batch <= 0 || !eps_dev || !log_alpha_dev || !partial_dev || !aligned4(partial_dev)) return CASSIE_EINVAL;
-  if (!cassie_sac::net_ok(actor) || !cassie_sac::net_ok(qf1) || !cassie_sac::net_ok(qf2)) return CASSIE_EINVAL;
+  if (!net_ok(actor) || !net_ok(qf1) || !net_ok(qf2)) return CASSIE_EINVAL;
   const Pool pool{pool_obs, nullptr, nullptr, nullptr, nullptr, pool_capacity};
-  const Net th = net_of(actor), q1 = net_of(qf1), q2 = net_of(qf2);
-  const dim3 grid(blocks_for(batch)), block(64 * WAVES);
-  hipStream_t s = (hipStream_t)stream;
-#define SAC_AG(D_, A_) hipLaunchKernelGGL((actor_grad_kernel<D_, A_>), grid, block, 0, s, pool, idx_dev, batch, th, q1, q2, eps_dev, log_alpha_dev, partial_dev)
-  if (obs_dim == 26 && act_dim == 6) SAC_AG(26, 6);
-  else if (obs_dim == 26 && act_dim == 7) SAC_AG(26, 7);
-  else if (obs_dim == 17 && act_dim == 6) SAC_AG(17, 6);
-  else if (obs_dim == 17 && act_dim == 7) SAC_AG(17, 7);
-  else return CASSIE_EINVAL;
-#undef SAC_AG
+  MLP32_LAUNCH(actor_grad_kernel, obs_dim, act_dim, blocks_for(batch), stream, pool, idx_dev, batch, net_of(actor), net_of(qf1), net_of(qf2), eps_dev, log_alpha_dev,
+               partial_dev);
   return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
 }
 
@@ -512,18 +483,13 @@ int CassieSacApply(int rows, int obs_dim, int act_dim, const float* partial_dev,
                    float beta1, float beta2, float eps, float* log_alpha_dev, float* alpha_m_dev, float* alpha_v_dev, int alpha_t, float alpha_lr,
                    float target_entropy, double* stats_dev, void* stream) {
   using namespace cassie_sac;
-  const int np = CassieSacParamCount(obs_dim, act_dim);
-  if (np == 0 || rows <= 0 || !partial_dev || !actor || !m_dev || !v_dev || t < 1 || !log_alpha_dev) return CASSIE_EINVAL;
-  const NetRW lv{actor[0], actor[1], actor[2], actor[3], actor[4], actor[5]};
-  if (!cassie_mlp32::net_ok(lv.W1, lv.b1, lv.W2, lv.b2, lv.W3, lv.b3)) return CASSIE_EINVAL;
+  if (CassieSacParamCount(obs_dim, act_dim) == 0 || rows <= 0 || !partial_dev || !net_ok(actor) || !m_dev || !v_dev || t < 1 || !log_alpha_dev) return CASSIE_EINVAL;
   if (alpha_m_dev && (!alpha_v_dev || alpha_t < 1)) return CASSIE_EINVAL;
-  const int Hh = 32;
   Offsets off;
-  off.o[0] = 0; off.o[1] = Hh * obs_dim; off.o[2] = off.o[1] + Hh; off.o[3] = off.o[2] + Hh * Hh; off.o[4] = off.o[3] + Hh; off.o[5] = off.o[4] + 2 * act_dim * Hh;
-  off.o[6] = np;
-  const auto coef = [&](double rate, int k) { return rate * sqrt(1.0 - pow((double)beta2, k)) / (1.0 - pow((double)beta1, k)); };
-  hipLaunchKernelGGL(apply_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, rows, partial_dev, scale, lv, off, m_dev, v_dev, (float)coef(lr, t), beta1, beta2,
-                     eps, log_alpha_dev, alpha_m_dev, alpha_v_dev, alpha_m_dev ? (float)coef(alpha_lr, alpha_t) : 0.0f, target_entropy, stats_dev);
+  actor_offsets(obs_dim, 2 * act_dim, off.o);
+  hipLaunchKernelGGL(apply_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, rows, partial_dev, scale, net_rw(actor), off, m_dev, v_dev,
+                     adam_step_size(lr, beta1, beta2, t), beta1, beta2, eps, log_alpha_dev, alpha_m_dev, alpha_v_dev,
+                     alpha_m_dev ? adam_step_size(alpha_lr, beta1, beta2, alpha_t) : 0.0f, target_entropy, stats_dev);
   return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
 }
 

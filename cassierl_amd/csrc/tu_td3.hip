@@ -199,10 +199,6 @@ __global__ void __launch_bounds__(64 * WAVES, 2) policy_step_kernel(const double
   }
 }
 
-inline Net net_of(const float* const* p) { return Net{p[0], p[1], p[2], p[3], p[4], p[5]}; }
-inline NetRW net_rw(float* const* p) { return NetRW{p[0], p[1], p[2], p[3], p[4], p[5]}; }
-template <class P> inline bool net_ok(P p) { return p && cassie_mlp32::net_ok(p[0], p[1], p[2], p[3], p[4], p[5]); }
-
 }  // namespace cassie_td3
 
 extern "C" {
@@ -210,17 +206,9 @@ extern "C" {
 int CassieTd3PolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* const* actor, const float* noise_dev, float sigma, const double* low_dev,
                         const double* high_dev, float* pool_obs_row_dev, float* pool_act_row_dev, double* env_actions_dev, void* stream) {
   using namespace cassie_td3;
-  if (!obs_dev || n <= 0 || !cassie_td3::net_ok(actor) || !noise_dev || !low_dev || !high_dev || !pool_obs_row_dev || !pool_act_row_dev || !env_actions_dev)
-    return CASSIE_EINVAL;
-  const Net th = net_of(actor);
-  const dim3 grid(((n + 31) / 32 + WAVES - 1) / WAVES), block(64 * WAVES);
-  hipStream_t s = (hipStream_t)stream;
-#define TD3_STEP(D_, A_) hipLaunchKernelGGL((policy_step_kernel<D_, A_>), grid, block, 0, s, obs_dev, n, th, noise_dev, sigma, low_dev, high_dev, pool_obs_row_dev, \
-                                            pool_act_row_dev, env_actions_dev)
-  if (obs_dim == 26 && act_dim == 6) TD3_STEP(26, 6);
-  else if (obs_dim == 26 && act_dim == 7) TD3_STEP(26, 7);
-  else return CASSIE_EINVAL;
-#undef TD3_STEP
+  if (!obs_dev || n <= 0 || !net_ok(actor) || !noise_dev || !low_dev || !high_dev || !pool_obs_row_dev || !pool_act_row_dev || !env_actions_dev) return CASSIE_EINVAL;
+  MLP32_LAUNCH_STEP(policy_step_kernel, obs_dim, act_dim, policy_step_grid(n), stream, obs_dev, n, net_of(actor), noise_dev, sigma, low_dev, high_dev, pool_obs_row_dev,
+                    pool_act_row_dev, env_actions_dev);
   return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
 }
 
@@ -231,19 +219,9 @@ int CassieTd3CriticGrad(const float* pool_obs, const float* pool_act, const floa
   using namespace cassie_td3;
   const Pool pool{pool_obs, pool_act, pool_rew, pool_term, pool_next_obs, pool_capacity};
   if (!pool_ok(pool) || !idx_dev || batch <= 0 || !eps_next_dev || !(noise_clip >= 0.0f) || !partial_dev || !aligned4(partial_dev)) return CASSIE_EINVAL;
-  if (!cassie_td3::net_ok(target_actor) || !cassie_td3::net_ok(target_qf1) || !cassie_td3::net_ok(target_qf2) || !cassie_td3::net_ok(qf1) || !cassie_td3::net_ok(qf2))
-    return CASSIE_EINVAL;
-  const Net ta = net_of(target_actor), t1 = net_of(target_qf1), t2 = net_of(target_qf2), q1 = net_of(qf1), q2 = net_of(qf2);
-  const dim3 grid(blocks_for(batch)), block(64 * WAVES);
-  hipStream_t s = (hipStream_t)stream;
-#define TD3_CQ(D_, A_) hipLaunchKernelGGL((critic_grad_kernel<D_, A_>), grid, block, 0, s, pool, idx_dev, batch, ta, t1, t2, q1, q2, eps_next_dev, policy_noise, \
-                                          noise_clip, discount, partial_dev)
-  if (obs_dim == 26 && act_dim == 6) TD3_CQ(26, 6);
-  else if (obs_dim == 26 && act_dim == 7) TD3_CQ(26, 7);
-  else if (obs_dim == 17 && act_dim == 6) TD3_CQ(17, 6);
-  else if (obs_dim == 17 && act_dim == 7) TD3_CQ(17, 7);
-  else return CASSIE_EINVAL;
-#undef TD3_CQ
+  if (!net_ok(target_actor) || !net_ok(target_qf1) || !net_ok(target_qf2) || !net_ok(qf1) || !net_ok(qf2)) return CASSIE_EINVAL;
+  MLP32_LAUNCH(critic_grad_kernel, obs_dim, act_dim, blocks_for(batch), stream, pool, idx_dev, batch, net_of(target_actor), net_of(target_qf1), net_of(target_qf2),
+               net_of(qf1), net_of(qf2), eps_next_dev, policy_noise, noise_clip, discount, partial_dev);
   return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
 }
 
@@ -253,15 +231,12 @@ int CassieTd3CriticApply(int rows, int obs_dim, int act_dim, const float* partia
   using namespace cassie_td3;
   const int np = CassieDdpgParamCount(obs_dim, act_dim, CASSIE_DDPG_CRITIC);
   if (np == 0 || rows <= 0 || !partial_dev || !m1_dev || !v1_dev || !m2_dev || !v2_dev || t < 1) return CASSIE_EINVAL;
-  if (!cassie_td3::net_ok(qf1) || !cassie_td3::net_ok(qf2) || !cassie_td3::net_ok(target_qf1) || !cassie_td3::net_ok(target_qf2)) return CASSIE_EINVAL;
+  if (!net_ok(qf1) || !net_ok(qf2) || !net_ok(target_qf1) || !net_ok(target_qf2)) return CASSIE_EINVAL;
   CriticPair pair;
   pair.side[0] = CriticSide{partial_dev, net_rw(qf1), net_rw(target_qf1), m1_dev, v1_dev, stats_dev};
   pair.side[1] = CriticSide{partial_dev + (size_t)rows * (np + 2), net_rw(qf2), net_rw(target_qf2), m2_dev, v2_dev, stats_dev ? stats_dev + 2 : nullptr};
-  const int Hh = 32;   // the critic's row, as CassieDdpgApply lays it out
-  int* o = pair.off;
-  o[0] = 0; o[1] = Hh * obs_dim; o[2] = o[1] + Hh; o[3] = o[2] + Hh * (Hh + act_dim); o[4] = o[3] + Hh; o[5] = o[4] + Hh; o[6] = np;
-  const double a = (double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t));
-  hipLaunchKernelGGL(critic_apply_kernel, dim3(2), dim3(1024), 0, (hipStream_t)stream, rows, scale, pair, (float)a, beta1, beta2, eps, tau);
+  critic_offsets(obs_dim, act_dim, pair.off);   // the critic's row, as CassieDdpgApply lays it out
+  hipLaunchKernelGGL(critic_apply_kernel, dim3(2), dim3(1024), 0, (hipStream_t)stream, rows, scale, pair, adam_step_size(lr, beta1, beta2, t), beta1, beta2, eps, tau);
   return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
 }
 
