@@ -585,6 +585,13 @@ int CassieVecTierInfo(CassieVec* h, uint64_t* out8) {
 }
 
 #ifdef CASSIE_PHASE_TIMING
+extern "C" int CassieVecPhaseMode() {  // what CassieVecPhaseCycles counts: 1 the whole Env.step, 2 the reset pass alone (a product build has neither function)
+#ifdef CASSIE_PHASE_RESET_ONLY
+  return 2;
+#else
+  return 1;
+#endif
+}
 extern "C" int CassieVecPhaseCycles(CassieVec* h, unsigned long long* out16) {  // profiling builds only; not part of the public ABI
   if (!h || !h->phase) return CASSIE_EINVAL;
   if (hipStreamSynchronize(h->stream) != hipSuccess) return CASSIE_EHIP;

@@ -648,8 +648,16 @@ template <class B> struct Duo : Core<B> {
   // carries out).
   // HF: the height-field instantiation (terrain collision stage in the set-up, contact frames along the local normal; the joint sweep itself does
   // not know: rows are rows).
+  // (profiling builds: a backend whose Lds keeps the reset pass's clocks apart is told where that pass begins and ends; any other Lds is not)
+  template <class L> static LEG_FN auto in_reset_pass(L& l, bool on, int) -> decltype(l.in_reset_pass(on)) { return l.in_reset_pass(on); }
+  template <class L> static LEG_FN void in_reset_pass(L&, bool, long) {}
   template <int MODE, bool HF = false, class IoOf>
   static LEG_FN void env_step2(const EnvCfg& cfg, typename B::Lds& lds, W ws, IoOf&& io_of, const M (&valid)[2], Out (&o)[2], const Terrain* hf = nullptr) {
+#ifdef CASSIE_TWO_OUTPUTS   // A/B and profiling builds: the generic form (reset pass, then a second outputs call) on the flat floor too
+    constexpr bool ONE_OUT = false;
+#else
+    constexpr bool ONE_OUT = !HF;   // one outputs section per Env.step (see the end of the loop)
+#endif
     const I leg = B::leg();
     const I lo = leg * 5 + 3, ao = leg * 3;
     const M left = leg == 0;
@@ -850,7 +858,10 @@ template <class B> struct Duo : Core<B> {
         sub++;
         if (sub < cfg.n_sub && more) continue;
       }
-      if (!cfg.want_obs) break;
+      if (!cfg.want_obs || (ONE_OUT && reset_pass)) break;
+      // ONE outputs section on the flat floor: the call after the last substep stores the reset observation of the environments it resets (it has
+      // just computed those values: step_outputs<true>), so the reset pass ends at its finish -- no second operational-space state, no round trip of
+      // the lane state around it.  The height-field instantiation keeps the two calls.
       lds.snapshot(true);
       bool again = false;
       lfor<0, 2>([&](auto gg) {
@@ -860,14 +871,20 @@ template <class B> struct Duo : Core<B> {
         Lane st;
         lds.mark(17);   // 17 = bookkeeping after the last substep
         get_lane(ws, G * W_GROUP, st);
-        if (C::step_outputs(cfg, lds, io, st, live[G], o[G], reset_pass)) again = true;
+        if (C::template step_outputs<ONE_OUT>(cfg, lds, io, st, live[G], o[G], reset_pass)) again = true;
         put_lane(ws, G * W_GROUP, st);
         B::fence();
         lds.mark(reset_pass ? 19 : 18);   // 18 = outputs of the step, 19 = outputs of the reset pass
       });
       if (reset_pass || !again) break;
       reset_pass = true;
+#ifdef CASSIE_PHASE_TIMING
+      lds.mark(0); in_reset_pass(lds, true, 0);   // (profiling builds with -DCASSIE_PHASE_RESET_ONLY keep the clocks of the reset pass alone)
+#endif
     }
+#ifdef CASSIE_PHASE_TIMING
+    lds.mark(0); in_reset_pass(lds, false, 0);
+#endif
     // ---- state write-back: q, v, warm start, clock, iteration count; the setState snapshot, the motor commands and qstate are in
     // the record already (written where they changed)
     lds.mark(20);

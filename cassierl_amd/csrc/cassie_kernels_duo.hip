@@ -84,11 +84,17 @@ struct DevDuoB : DevB {
     int lo, ao;
 #ifdef CASSIE_PHASE_TIMING   // profiling builds (tools/phase_profile.py duo): shader cycles per phase of this wavefront; the time up to mark(k) goes to bucket k
     unsigned long long t_last, acc[16];
+    bool rp = false;   // the pass that is running is the reset pass (env_step2)
+    LEG_FN void in_reset_pass(bool on) { rp = on; }
     LEG_FN void mark(int k) {
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       const unsigned long long n = __builtin_readcyclecounter();
-      acc[k < 16 ? k : 0] += n - t_last; t_last = n;
+#ifdef CASSIE_PHASE_RESET_ONLY   // the buckets of the reset pass alone (tools/phase_profile_duo.py); bucket 0 = its glue (with two outputs calls -- terrain -- the second call too)
+      if (rp)
+#endif
+      acc[k < 16 ? k : 0] += n - t_last;
+      t_last = n;
       __builtin_amdgcn_sched_barrier(0);
     }
 #else

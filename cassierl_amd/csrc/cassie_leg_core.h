@@ -1181,6 +1181,9 @@ template <class B> struct Core {
   // Observation / reward / termination of the environments of `live`, stores, and the state of a terminated environment set to the
   // reset pose.  Returns true when the caller has to run the reset pass (mj_forward only, for o.do_reset) and call this again with
   // reset_pass = true, which stores the reset observation (and returns false).
+  // ONE_SECTION (cassie_duo_core.h, flat floor): there is no second call.  This call stores the reset observation of the environments it resets
+  // itself -- see the end of the function -- and the caller's reset pass only has to leave the warm start.
+  template <bool ONE_SECTION = false>
   static LEG_FN bool step_outputs(const EnvCfg& cfg, typename B::Lds& lds, const Io& io, Lane& st, M live, Out& o, bool reset_pass) {
     const I leg = B::leg();
     const I lo = leg * 5 + 3;
@@ -1303,6 +1306,25 @@ template <class B> struct Core {
       lds.cst(C_QST + Dd, qi, o.do_reset);
     });
     lds.cst(C_TIME, D(0.0), o.do_reset);
+    if constexpr (ONE_SECTION) {
+      // The reset observation (what the second call stores): the 17 operational-space values of the LAST setState with the pitch and pitch rate of
+      // the reset pose, trajectory slots zero.  The reset pass does no setState, so the snapshot the second call reads is the one this call has just
+      // used -- ob / of above are its values -- except where this call re-wrote it (failure guard: the reset pose at rest) or does not read it
+      // (FLAG_FIX_STALE_KIN: the state, by then the reset pose at rest).  Those lanes (`own`) take the operational-space state of `st`, which holds
+      // the reset pose at rest on every lane of do_reset from here on.
+      // The row just stored is overwritten for the lanes of do_reset (same lane, same address, program order).
+      const M rs = o.do_reset;
+      const M own = fix_kin ? rs : (rs & bad);
+      if (B::any(own)) {
+        D body1[4], foot1[4];
+        opstate(st.qb, st.ql, st.vb, st.vl, body1, foot1);
+        ob[0] = B::sel(own, body1[1], ob[0]); ob[2] = B::sel(own, body1[2], ob[2]); ob[3] = B::sel(own, body1[3], ob[3]);
+        of[0] = B::sel(own, foot1[0] - body1[0], of[0]); of[1] = B::sel(own, foot1[1], of[1]); of[3] = B::sel(own, foot1[2], of[3]); of[4] = B::sel(own, foot1[3], of[4]);
+      }
+      ob[1] = st.qb[2]; ob[4] = st.vb[2];
+      put(io.obs, rs);
+      lfor<0, 9>([&](auto ii) { constexpr int Ii = decltype(ii)::value; B::pst(io.obs, I(17 + Ii), D(0.0), rs & !left); });
+    }
     return true;   // the reset pose on the flat floor has 12 rows: never an overflow
   }
 

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Phase breakdown of the 64-environments-per-wavefront kernel on the bench workload (not a test).  Needs a profiling build of tu_duo
 (profiles/tools/ab_build_units.sh phase "tu_duo" -ffp-contract=on -DCASSIE_PHASE_TIMING) pointed to by CASSIE2D_LIB; prints shader cycles per
-phase and wavefront per Env.step.  The clocks wait for outstanding memory operations at every mark (a store's latency lands in its phase)."""
+phase and wavefront per Env.step.  The clocks wait for outstanding memory operations at every mark (a store's latency lands in its phase).
+A build with -DCASSIE_PHASE_RESET_ONLY on top keeps the clocks of the RESET PASS alone; the library says which of the two it is
+(CassieVecPhaseMode) and the title repeats it.  Bucket 0 is then the reset pass's glue (on terrain, where the reset pass has its own outputs call, that too)."""
 import ctypes as ct
 import os
 import sys
@@ -24,6 +26,9 @@ env.set_trajectory(g.time, g.qpos)
 out = env.alloc(); env.reset(out)
 ids = torch.arange(n, device="cuda")
 buf = (ct.c_ulonglong * 16)()
+if not hasattr(env.L, "CassieVecPhaseCycles"):
+    sys.exit("this library is not a profiling build (-DCASSIE_PHASE_TIMING)")
+reset_only = hasattr(env.L, "CassieVecPhaseMode") and env.L.CassieVecPhaseMode() == 2
 env.L.CassieVecPhaseCycles.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
 lo, hi = env.action_space.low, env.action_space.high
 if mode == "OSC":
@@ -43,7 +48,7 @@ names = {0: "glue: load, bookkeeping, outputs, op-space state, write-back", 15: 
          8: "generalised force from the rows' geometry", 9: "M^-1 g, implicit damping, integration", 14: "state out"}
 waves = n / 64
 tot = v.sum()
-print("%s env, %s, %d envs: %.0f cycles per wavefront per Env.step (%.3f ms at 2.4 GHz)%s" % (kind, mode, n, tot / waves / steps, tot / waves / steps / 2.4e6,
+print("%s%s env, %s, %d envs: %.0f cycles per wavefront per Env.step (%.3f ms at 2.4 GHz)%s" % ("RESET PASS ONLY: " if reset_only else "", kind, mode, n, tot / waves / steps, tot / waves / steps / 2.4e6,
       "; per one-substep launch: %.0f cycles = %.1f us" % (tot / waves / steps / 10, tot / waves / steps / 10 / 2.4e3) if mode == "OSC" else ""))
 for k in (0, 15, 1, 2, 3, 4, 5, 6, 10, 11, 7, 12, 13, 8, 9, 14):
     print("  %2d %-64s %9.0f cycles  %6.2f %%" % (k, names[k], v[k] / waves / steps, 100 * v[k] / tot))
