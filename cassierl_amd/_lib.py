@@ -41,6 +41,8 @@ EXPORTS = [
     "CassieTd3PolicyStep", "CassieTd3CriticGrad", "CassieTd3CriticApply",
     # PPO (include/cassie_trpo.h)
     "CassieTrpoGae", "CassieTrpoClipGradRows", "CassieTrpoClipGrad", "CassiePgClipGradRows", "CassiePgClipGrad",
+    # ES (include/cassie_trpo.h)
+    "CassieEsParamCount", "CassieEsPairsPerWorkgroup", "CassieEsPolicyStep", "CassieEsBook", "CassieEsGradRows", "CassieEsGrad",
 ]
 
 

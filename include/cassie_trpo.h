@@ -294,6 +294,39 @@ int CassiePgClipGrad(const float* obs_dev, int n, int obs_dim, int act_dim, cons
                      const float* old_mean_dev, const float* log_std_old, const float* log_std_new, float clip, float scale, float* partial_dev,
                      double* stats_dev, void* stream);
 
+/* ---- ES (cassierl_amd/es.py, csrc/tu_es.hip): antithetic perturbations of the 32 x 32 tanh mean network drawn from a shared noise table.
+ * theta [P] is the mean network's parameter row [W1 | b1 | W2 | b2 | W3 | b3] (row-major as torch.nn.Linear), P = CassieEsParamCount; table
+ * [table_len] float32 holds standard normal numbers; direction d is eps_d = table[offsets[d] : offsets[d] + P].  Environment i evaluates
+ * direction i >> 1 with sign +1 (i even) or -1 (i odd).  Every offset must lie in [0, table_len - P] (CassieEsGrad: table_len - n_params):
+ * the kernels do NOT check them (cassierl_amd/es.py: EsKernels.set_directions does, on the host, before anything is launched). */
+
+/* parameters of the mean network, as CassieTrpoParamCount; 0 for an unsupported shape (supported: obs_dim 26 or 17, act_dim 6 or 7) */
+int CassieEsParamCount(int obs_dim, int act_dim);
+/* pairs of environments that one workgroup of CassieEsPolicyStep evaluates (its grid is ceil(n / 2 / this)) */
+int CassieEsPairsPerWorkgroup(void);
+
+/* One policy step of the whole population in ONE launch; n even, obs float64 [n][obs_dim] as the environment wrote it:
+ *   w_i = theta + (s_i sigma) eps_(i >> 1),  mean_i = W3 tanh(W2 tanh(W1 obs_i + b1) + b2) + b3 with the layers cut out of w_i,
+ *   act_i = alive[i] ? mean_i : 0  (alive NULL: every environment is alive),
+ *   env_actions float64 [n][act_dim] = clip(low + (act + 1) / 2 * (high - low), low, high): a dead environment gets the middle of the box.
+ * A pair with both environments dead reads nothing from the table.  Nothing but env_actions[0 : n] is written; a call repeats bit for bit.
+ * CASSIE_EINVAL: odd n, table_len < P, a null pointer (other than alive), an unsupported shape. */
+int CassieEsPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* theta_dev, const float* table_dev, long long table_len,
+                       const long long* offsets_dev, float sigma, const unsigned char* alive_dev, const double* low_dev, const double* high_dev,
+                       double* env_actions_dev, void* stream);
+
+/* Bookkeeping of one Env.step of the population in one launch, with rew / done as CassieVecStep wrote them:
+ *   fitness[i] += alive[i] ? rew[i] : 0;  length[i] += alive[i];  alive[i] &= !done[i]   (alive: one byte, 0 / 1). */
+int CassieEsBook(const double* rew_dev, const unsigned char* done_dev, int n, unsigned char* alive_dev, double* fitness_dev, long long* length_dev, void* stream);
+
+/* The weighted sum of m directions: partial [rows][n_params] float32, rows = CassieEsGradRows(m);
+ *   partial[r][k] = sum over the directions d of row r, ascending, of w[d] table[offsets[d] + k]   (a float32 fmaf chain from 0),
+ * row r holding the directions [r c, min(m, (r + 1) c)), c = ceil(m / rows) (a row past m is all zero).  Any n_params >= 1.  The caller adds the
+ * rows; a call repeats bit for bit. */
+int CassieEsGradRows(int m);
+int CassieEsGrad(const float* table_dev, long long table_len, const long long* offsets_dev, const float* w_dev, int m, int n_params, float* partial_dev,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

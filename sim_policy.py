@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Counterpart of rllab/envs/sim_policy.py:19-31 on the batched MI355X environment: load a snapshot written by train_trpo.py,
-train_vpg.py, train_ddpg.py, train_sac.py or train_td3.py (`--snapshot`, snapshot_mode="last"; a VPG snapshot carries its policy's hidden sizes, a DDPG or TD3 snapshot is rolled out with mu(s), a SAC snapshot with tanh of the Gaussian's mean or sample) and roll the policy out -- no training.  The reference animates ONE env through rllab's
+train_vpg.py, train_ddpg.py, train_sac.py, train_td3.py or train_es.py (`--snapshot`, snapshot_mode="last"; a VPG snapshot carries its policy's hidden sizes, a DDPG or TD3 snapshot is rolled out with mu(s), a SAC snapshot with tanh of the Gaussian's mean or sample, an ES snapshot with the unperturbed mean on an even number of envs) and roll the policy out -- no training.  The reference animates ONE env through rllab's
 `rollout(env, policy, max_path_length, animated=True)`; here N resident envs run the same loop in parallel (there is no
 viewer: GUI is out of scope) and the script prints what the reference's loop would let one read off the screen: path
 lengths and returns.
@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("file", help="snapshot written by train_trpo.py, train_vpg.py or train_ddpg.py --snapshot")
+    ap.add_argument("file", help="snapshot written by --snapshot of train_trpo.py, train_vpg.py, train_ppo.py, train_ddpg.py, train_sac.py, train_td3.py or train_es.py")
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--max-path-length", type=int, default=1000)   # sim_policy.py:14 default
     ap.add_argument("--kind", default="walk", choices=["walk", "stand"])
@@ -45,6 +45,13 @@ def main():
         from cassierl_amd.ppo import make_cassie_ppo
         algo = make_cassie_ppo(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
                                terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (128, 128))), batch_size=args.envs, minibatch_size=args.envs)
+    elif ck.get("algo") == "es":   # a train_es.py snapshot: the unperturbed parameters, rolled out with the mean (the noise table is the snapshot's)
+        from cassierl_amd.es import make_cassie_es
+        if args.envs % 2:
+            ap.error("an ES snapshot needs an even --envs (two environments per direction), got %d" % args.envs)
+        algo = make_cassie_es(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed, terrain=terrain,
+                              hidden_sizes=tuple(ck.get("hidden_sizes", (32, 32))), table_size=ck["table_size"], table_seed=ck["table_seed"])
+        args.deterministic = True
     elif ck.get("algo") == "ddpg":   # a train_ddpg.py snapshot: the deterministic actor mu(s); only the policy is loaded, so the smallest pool will do
         from cassierl_amd.ddpg import make_cassie_ddpg
         algo = make_cassie_ddpg(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
