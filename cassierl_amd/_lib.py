@@ -130,3 +130,45 @@ def load():
     L.Cassie2dInit.restype = ct.c_void_p
     _LIB = L
     return L
+
+
+def available(*symbols):
+    """Whether the HIP extension is there and exports every one of `symbols`: the one answer to "kernels or the torch statements"."""
+    try:
+        L = load()
+    except OSError:
+        return False
+    return all(hasattr(L, s) for s in symbols)
+
+
+def ptr(t):
+    """A tensor's device pointer as a library argument (None stays a null pointer)."""
+    return None if t is None else ct.c_void_p(t.data_ptr())
+
+
+class Kernels:
+    """Base of every kernel-call class (trpo.py, ppo.py, es.py, offpolicy.py): ENTRY names the exported functions, every call goes through the
+    dict `fn` (key -> function, filled from ENTRY and looked up at call time, so a test can wrap or count its entries), and a non-zero return
+    code raises RuntimeError("<symbol> failed (%d)").  `entry`: this object's own ENTRY (a launcher whose symbol depends on the policy's width);
+    `fn`: a dict shared with another object."""
+
+    ENTRY = {}           # key in `fn` -> exported name
+    STREAM_LAST = True   # _call appends the current stream of `dev` as the last argument
+
+    def __init__(self, dev, fn=None, entry=None):
+        if entry is not None:
+            self.ENTRY = entry
+        self.L, self.dev = load(), dev
+        self.fn = {} if fn is None else fn
+        self.fn.update({k: getattr(self.L, name) for k, name in self.ENTRY.items()})
+
+    _p = staticmethod(ptr)
+
+    def _stream(self):
+        import torch
+        return ct.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def _call(self, key, *args):
+        rc = self.fn[key](*args, self._stream()) if self.STREAM_LAST else self.fn[key](*args)
+        if rc != 0:
+            raise RuntimeError("%s failed (%d)" % (self.ENTRY[key], rc))

@@ -34,10 +34,9 @@ import time
 
 import torch
 
-from . import terrain as terrain_lib
-from .trpo import (TRPO, GaussianMLPPolicy, LinearFeatureBaseline, NormalizedActions, _world, all_sum_, broadcast_initial_policy, flat_params,
-                   hidden_sizes_of, set_flat_params)
-from .vpg import _two_layer_tanh, adam_step_, fused_adam_step_
+from ._lib import Kernels, available, ptr
+from .trpo import (TRPO, FlatAdam, NormalizedActions, _two_layer_tanh, _world, all_sum_, broadcast_initial_policy, flat_params, gaussian_policy_nets,
+                   make_cassie_algo, set_flat_params)
 
 
 # --------------------------------------------------------------------------------------------- the torch statements
@@ -112,7 +111,7 @@ def pair_weights(u):
 
 
 # --------------------------------------------------------------------------------------------- the kernel-call layer
-class EsKernels:
+class EsKernels(Kernels):
     """The library calls of ES on one noise table (csrc/tu_es.hip).  ENTRY names the exported functions; every call goes through the dict `fn` (key ->
     function, looked up at call time, so a test can wrap its entries).  The kernels do not check offsets: set_directions does, on the host, with
     one read-back, and raises before anything is launched.  ValueError for an unsupported shape or a table that is not a contiguous float32 vector."""
@@ -121,9 +120,7 @@ class EsKernels:
              "GradRows": "CassieEsGradRows", "Grad": "CassieEsGrad"}
 
     def __init__(self, table, n_envs, obs_dim, act_dim, low=None, high=None):
-        from . import _lib
-        self.L = _lib.load()
-        self.fn = {k: getattr(self.L, name) for k, name in self.ENTRY.items()}
+        super().__init__(table.device)
         self.D, self.A, self.n = int(obs_dim), int(act_dim), int(n_envs)
         self.P = self.fn["ParamCount"](self.D, self.A)
         if self.P == 0:
@@ -132,19 +129,11 @@ class EsKernels:
             raise ValueError("EsKernels: the number of environments must be positive and even, got %d" % self.n)
         if table.dtype != torch.float32 or table.dim() != 1 or not table.is_contiguous() or table.numel() < self.P:
             raise ValueError("EsKernels: the table must be a contiguous float32 vector of at least %d entries" % self.P)
-        self.table, self.dev = table, table.device
+        self.table = table
         self.low, self.high = low, high
         self.offsets, self._dir_np = None, 0
         self._partial = {}
         self.env_actions = None
-
-    def _stream(self):
-        return ct.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-
-    def _call(self, name, *args):
-        rc = self.fn[name](*args, self._stream())
-        if rc != 0:
-            raise RuntimeError("%s failed (%d)" % (self.ENTRY[name], rc))
 
     def set_directions(self, offsets, n_params=None):
         """The directions of the calls that follow: offsets [n_envs / 2] int64, contiguous, on the table's device, every one in
@@ -182,9 +171,9 @@ class EsKernels:
                 self.env_actions = torch.empty((self.n, self.A), dtype=torch.float64, device=self.dev)
             out = self.env_actions
         assert out.dtype == torch.float64 and out.is_contiguous() and out.shape == (self.n, self.A)
-        P = lambda t: ct.c_void_p(t.data_ptr())
+        P = ptr
         self._call("PolicyStep", P(obs), self.n, self.D, self.A, P(theta), P(self.table), ct.c_longlong(self.table.numel()), P(self.offsets), ct.c_float(sigma),
-                   None if alive is None else P(alive), P(self.low), P(self.high), P(out))
+                   P(alive), P(self.low), P(self.high), P(out))
         return out
 
     def book(self, rew, done, alive, fitness, length):
@@ -193,7 +182,7 @@ class EsKernels:
         for t, dt in ((rew, torch.float64), (done, torch.uint8), (alive, torch.uint8), (fitness, torch.float64), (length, torch.int64)):
             if t.dtype != dt or not t.is_contiguous() or t.numel() != n or t.device != self.dev:
                 raise TypeError("CassieEsBook: contiguous rew / fitness float64, done / alive uint8, length int64 of %d entries on %s" % (n, self.dev))
-        P = lambda t: ct.c_void_p(t.data_ptr())
+        P = ptr
         self._call("Book", P(rew), P(done), n, P(alive), P(fitness), P(length))
 
     def grad(self, w):
@@ -206,7 +195,7 @@ class EsKernels:
         if (m, k) not in self._partial:
             self._partial[m, k] = torch.empty((self.fn["GradRows"](m), k), dtype=torch.float32, device=self.dev)
         partial = self._partial[m, k]
-        P = lambda t: ct.c_void_p(t.data_ptr())
+        P = ptr
         self._call("Grad", P(self.table), ct.c_longlong(self.table.numel()), P(self.offsets), P(w), m, k, P(partial))
         return partial.sum(0)
 
@@ -218,10 +207,11 @@ def make_table(size, seed, device):
 
 
 # --------------------------------------------------------------------------------------------- ES
-class ES(TRPO):
+class ES(FlatAdam, TRPO):
     """ES on TRPO's snapshot machinery and gather; the baseline is unused.  Switches (attributes, default True) that tests set to force the torch
     statements: fused_policy_step (CassieEsPolicyStep), fused_book (CassieEsBook), fused_grad (CassieEsGrad), fused_adam (CassiePgAdam).
     last_policy_step_kind ("es_step" / "torch"), last_book_fused, last_grad_kind ("es_grad" / "torch") and last_adam_fused say what ran."""
+    ALGO = "es"
 
     def __init__(self, env_step, env_reset, policy, baseline, n_envs, obs_dim, act_map, sigma=0.02, learning_rate=0.01, l2_coeff=0.005, max_path_length=1000,
                  table_size=1 << 24, table_seed=None, fitness_shaping="centered_rank", beta1=0.9, beta2=0.999, epsilon=1e-8, seed=1, env_reset_masked=None,
@@ -233,9 +223,8 @@ class ES(TRPO):
         if self.env_id0 % 2:
             raise ValueError("ES: a shard must start on an even environment id, got %d" % self.env_id0)
         shape_fitness(torch.zeros(2), fitness_shaping)
-        self.sigma, self.learning_rate, self.l2_coeff, self.fitness_shaping = float(sigma), float(learning_rate), float(l2_coeff), fitness_shaping
-        self.beta1, self.beta2, self.epsilon = beta1, beta2, epsilon
-        self.adam_t, self.adam_m, self.adam_v = 0, None, None
+        self._adam_init(float(learning_rate), beta1, beta2, epsilon)
+        self.sigma, self.l2_coeff, self.fitness_shaping = float(sigma), float(l2_coeff), fitness_shaping
         self.n_params = sum(p.numel() for p in policy.mean_net.parameters())
         self.table_size, self.table_seed = int(table_size), int(seed * 1000003 + 15485863 if table_seed is None else table_seed)
         if self.table_size < self.n_params:
@@ -246,11 +235,7 @@ class ES(TRPO):
         self.gen_off.manual_seed(seed * 1000003 + 32452843)
         self.offsets = None
         self._ek = None
-        self.last_policy_step_kind = self.last_grad_kind = self.last_adam_fused = self.last_book_fused = None
-
-    @property
-    def hidden_sizes(self):
-        return hidden_sizes_of(self.policy)
+        self.last_policy_step_kind = self.last_grad_kind = self.last_book_fused = None
 
     def _kernels(self):
         """EsKernels for this run when they apply -- CUDA, a float32 two-layer tanh policy with 32 x 32 hidden units of a supported shape, rllab's
@@ -266,12 +251,8 @@ class ES(TRPO):
         A = lin[2].out_features
         if lin[0].in_features != self.obs_dim or not all(t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == A for t in (low, high)):
             return None
-        try:   # no library, or one without the symbols: the torch statements.  Anything else EsKernels objects to is a mistake and raises.
-            from . import _lib
-            L = _lib.load()
-        except OSError:
-            return None
-        if not all(hasattr(L, name) for name in EsKernels.ENTRY.values()) or L.CassieEsParamCount(self.obs_dim, A) == 0:
+        # no library, one without the symbols or an unsupported shape: the torch statements.  Anything else EsKernels objects to is a mistake and raises.
+        if not available(*EsKernels.ENTRY.values()) or Kernels(p.device, entry={"ParamCount": "CassieEsParamCount"}).fn["ParamCount"](self.obs_dim, A) == 0:
             return None
         self._ek = None   # (a refusal below is raised again by the next call, not remembered as 'torch')
         self._ek = EsKernels(self.table, self.n_envs, self.obs_dim, A, low, high)
@@ -338,14 +319,8 @@ class ES(TRPO):
         w = pair_weights(shape_fitness(all_fitness, self.fitness_shaping))[d0:d0 + m]
         g = all_sum_(self.local_gradient_sum(w).contiguous(), "gradient_all_reduce") * (1.0 / (2.0 * m_global * self.sigma))
         descent = self.l2_coeff * theta - g
-        if self.adam_m is None:
-            self.adam_m, self.adam_v = torch.zeros_like(theta), torch.zeros_like(theta)
         before = theta.clone()
-        self.adam_t += 1
-        fused = getattr(self, "fused_adam", True) and theta.is_cuda and theta.dtype == torch.float32
-        (fused_adam_step_ if fused else adam_step_)(theta, descent.contiguous(), self.adam_m, self.adam_v, self.adam_t, self.learning_rate, self.beta1, self.beta2,
-                                                    self.epsilon)
-        self.last_adam_fused = fused
+        self.adam_step(theta, descent.contiguous())
         set_flat_params(net, theta)
         return g.double().norm(), (theta - before).double().norm()
 
@@ -373,22 +348,14 @@ class ES(TRPO):
     # ---- snapshot: TRPO's, plus the algorithm, the policy shape, the hyper-parameters, the Adam state, the table's seed and size (never the
     # table) and the offset generator
     def _snapshot_fields(self):
-        return dict(algo="es", hidden_sizes=list(self.hidden_sizes), sigma=self.sigma, learning_rate=self.learning_rate, l2_coeff=self.l2_coeff,
-                    fitness_shaping=self.fitness_shaping, max_path_length=int(self.max_path_length), adam_t=int(self.adam_t),
-                    adam_m=None if self.adam_m is None else self.adam_m.detach().cpu(), adam_v=None if self.adam_v is None else self.adam_v.detach().cpu(),
-                    table_seed=int(self.table_seed), table_size=int(self.table_size), gen_off_state=self.gen_off.get_state())
+        return dict(super()._snapshot_fields(), sigma=self.sigma, learning_rate=self.learning_rate, l2_coeff=self.l2_coeff, fitness_shaping=self.fitness_shaping,
+                    max_path_length=int(self.max_path_length), **self._adam_snapshot(), table_seed=int(self.table_seed), table_size=int(self.table_size),
+                    gen_off_state=self.gen_off.get_state())
 
     def _load_fields(self, ck):
-        algo = ck.get("algo", "trpo")
-        if algo != "es":
-            raise ValueError("ES.load: the snapshot was written by %s, this run is es" % algo)
-        theirs, mine = tuple(ck.get("hidden_sizes", (32, 32))), self.hidden_sizes
-        if theirs != mine:
-            raise ValueError("ES.load: the snapshot's policy has hidden sizes %r, this run's has %r" % (theirs, mine))
+        super()._load_fields(ck)
+        self._adam_load(ck)
         dev = next(self.policy.parameters()).device
-        self.adam_t = int(ck.get("adam_t", 0))
-        self.adam_m = None if ck.get("adam_m") is None else ck["adam_m"].to(dev)
-        self.adam_v = None if ck.get("adam_v") is None else ck["adam_v"].to(dev)
         seed, size = int(ck.get("table_seed", self.table_seed)), int(ck.get("table_size", self.table_size))
         if (seed, size) != (self.table_seed, self.table_size):   # the table is part of the run: regenerated from the snapshot's seed
             self.table_seed, self.table_size = seed, size
@@ -403,22 +370,5 @@ def make_cassie_es(n_envs, kind="walk", control_mode="PD", device=0, trajectory=
     """ES on the batched MI355X environment; the counterpart of ppo.make_cassie_ppo (same env and sync_policy rules).  With a terrain library both
     environments of a pair stand on the same field (ids drawn over env_ids // 2): otherwise the antithetic difference would measure the ground,
     not the perturbation."""
-    from .vec_env import CassieVecEnv
-    env = CassieVecEnv(n_envs, kind=kind, control_mode=control_mode, n_substeps=10, auto_reset=True, device=device, trajectory=trajectory)
-    env.use_torch_stream()
-    dev = "cuda:%d" % device
-    bufs = env.alloc()
-    torch.manual_seed(seed)
-    obs_w = env.observation_space.shape[0]
-    policy = GaussianMLPPolicy(obs_w, env.adim, tuple(hidden_sizes), init_std=1.0).to(dev)
-    act_map = NormalizedActions(env.action_space.low, env.action_space.high, dev)
-    algo = ES(lambda a: env.step(a, bufs), lambda: env.reset(bufs), policy, LinearFeatureBaseline(), n_envs, obs_w, act_map, seed=seed,
-              env_reset_masked=lambda m: env.reset(bufs, mask=m), **kw)
-    algo.env = env
-    algo.terrain_spec = terrain
-    if terrain is not None:
-        env.set_terrain_library(terrain_lib.library_of_spec(terrain), terrain_lib.DEFAULT_SIZE[:2])
-        env.set_terrain_ids(terrain_lib.assign_terrains(terrain["seed"], algo.env_ids // 2, len(terrain["files"])).to(dev))
-    if sync_policy:
-        broadcast_initial_policy(algo)
-    return algo
+    return make_cassie_algo(ES, gaussian_policy_nets(hidden_sizes, 1.0), broadcast_initial_policy, n_envs, kind, control_mode, device, trajectory, seed, terrain,
+                            sync_policy, terrain_ids=lambda ids: ids // 2, **kw)

@@ -27,9 +27,8 @@ import ctypes as ct
 import torch
 import torch.distributed as dist
 
-from . import terrain as terrain_lib
-from .trpo import TRPO, NormalizedActions, _world, all_mean_, all_sum_, flat_params, set_flat_params
-from .vpg import adam_step_
+from ._lib import Kernels, available, ptr as _P
+from .trpo import TRPO, NormalizedActions, _world, adam_step_, all_mean_, all_sum_, flat_params, make_cassie_algo, set_flat_params
 
 
 class ReplayPool:
@@ -100,10 +99,6 @@ def _ptrs(net):
     return (ct.c_void_p * 6)(*[p.data_ptr() for p in ps])
 
 
-def _P(t):
-    return ct.c_void_p(t.data_ptr())
-
-
 def _F(*xs):
     return [ct.c_float(x) for x in xs]
 
@@ -112,30 +107,18 @@ class _NoBaseline:
     coeffs = None
 
 
-class PoolKernels:
-    """Base of DdpgKernels, SacKernels and Td3Kernels: the library calls of one update on the networks' own storage.  ENTRY names the exported
-    functions; every call goes through the dict `fn` (key -> function, looked up at call time, so a test can wrap its entries)."""
+class PoolKernels(Kernels):
+    """Base of DdpgKernels, SacKernels and Td3Kernels: the library calls of one update on the networks' own storage (_lib.Kernels: ENTRY, `fn`,
+    _call; the call sites pass the stream themselves, where the kernel takes one)."""
 
-    ENTRY = {}   # key in `fn` -> exported name
+    STREAM_LAST = False
 
     def __init__(self, nets, fn=None):
-        from . import _lib
-        self.L = _lib.load()
-        self.fn = {} if fn is None else fn   # Td3Kernels shares the dict of the DdpgKernels it embeds
-        self.fn.update({k: getattr(self.L, name) for k, name in self.ENTRY.items()})
+        super().__init__(next(nets[0].parameters()).device, fn)   # Td3Kernels shares the dict of the DdpgKernels it embeds
         for net in nets:
             if not all(p.is_contiguous() for p in net.parameters()):
                 raise ValueError("%s: contiguous parameters" % type(self).__name__)
-        self.dev = next(nets[0].parameters()).device
         self._partial = {}
-
-    def _stream(self):
-        return ct.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-
-    def _call(self, name, *args):
-        rc = self.fn[name](*args)
-        if rc != 0:
-            raise RuntimeError("%s failed (%d)" % (self.ENTRY[name], rc))
 
     def _rows(self, key, batch, *shape):
         """The cached buffer `key` of partial sums for this batch size: shape with -1 standing for the rows CassieDdpgPartialRows gives."""
@@ -263,12 +246,10 @@ class OffPolicy(TRPO):
         low, high, n, D, A = self.act_map.low, self.act_map.high, self.n_envs, self.obs_dim, self.act_dim
         if not all(t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == A for t in (low, high)):
             return None
-        try:
-            from . import _lib
-            L = _lib.load()
-            step_fn, commit_fn = getattr(L, self.STEP_ENTRY), L.CassieDdpgPoolCommit
-        except (OSError, AttributeError):
+        if not available(self.STEP_ENTRY, "CassieDdpgPoolCommit"):
             return None
+        k = Kernels(dev, entry={"Step": self.STEP_ENTRY, "Commit": "CassieDdpgPoolCommit"})
+        step_fn, commit_fn = k.fn["Step"], k.fn["Commit"]
         if not hasattr(self, "_env_actions") or self._env_actions.shape != (n, A):
             self._env_actions = torch.empty((n, A), dtype=torch.float64, device=dev)
         pool = self.pool
@@ -434,26 +415,8 @@ def broadcast_initial_networks(algo):
 
 def make_cassie_offpolicy(cls, make_nets, n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, terrain=None, sync_policy=True,
                           replay_pool_size=None, **kw):
-    """cls on the batched MI355X environment; the counterpart of vpg.make_cassie_vpg (same env, terrain and sync_policy rules).  make_nets(obs_dim,
-    act_dim) -> the networks of cls's constructor, the policy first, built after torch.manual_seed(seed).  replay_pool_size: rows of this rank's
-    pool (default: rllab's 1 000 000 rounded up to a multiple of n_envs; a row is 4 (2 D + A + 2) bytes)."""
-    from .vec_env import CassieVecEnv
-    env = CassieVecEnv(n_envs, kind=kind, control_mode=control_mode, n_substeps=10, auto_reset=True, device=device, trajectory=trajectory)
-    env.use_torch_stream()
-    dev = "cuda:%d" % device
-    bufs = env.alloc()
-    torch.manual_seed(seed)
-    obs_w = env.observation_space.shape[0]
-    nets = [net.to(dev) for net in make_nets(obs_w, env.adim)]
-    act_map = NormalizedActions(env.action_space.low, env.action_space.high, dev)
-    algo = cls(lambda a: env.step(a, bufs), lambda: env.reset(bufs), *nets, n_envs, obs_w, act_map, seed=seed,
-               replay_pool_size=default_pool_size(n_envs) if replay_pool_size is None else replay_pool_size,
-               env_reset_masked=lambda m: env.reset(bufs, mask=m), **kw)
-    algo.env = env
-    algo.terrain_spec = terrain
-    if terrain is not None:
-        env.set_terrain_library(terrain_lib.library_of_spec(terrain), terrain_lib.DEFAULT_SIZE[:2])
-        env.set_terrain_ids(terrain_lib.assign_terrains(terrain["seed"], algo.env_ids, len(terrain["files"])).to(dev))
-    if sync_policy:
-        broadcast_initial_networks(algo)
-    return algo
+    """cls on the batched MI355X environment (trpo.make_cassie_algo: env, terrain and sync_policy rules).  make_nets(obs_dim, act_dim) -> the networks
+    of cls's constructor, the policy first, built after torch.manual_seed(seed).  replay_pool_size: rows of this rank's pool (default: rllab's
+    1 000 000 rounded up to a multiple of n_envs; a row is 4 (2 D + A + 2) bytes)."""
+    return make_cassie_algo(cls, lambda D, A, dev: [net.to(dev) for net in make_nets(D, A)], broadcast_initial_networks, n_envs, kind, control_mode, device,
+                            trajectory, seed, terrain, sync_policy, replay_pool_size=default_pool_size(n_envs) if replay_pool_size is None else replay_pool_size, **kw)

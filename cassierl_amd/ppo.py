@@ -19,15 +19,15 @@ statements in this module are the specification, the kernels of csrc/tu_ppo.hip 
 
 The sampler, exploration noise, baseline kernels and snapshot machinery are TRPO's (cassierl_amd/trpo.py), unchanged.
 """
+import ctypes as ct
 import math
 
 import torch
 import torch.distributed as dist
 
-from . import terrain as terrain_lib
-from .trpo import (TRPO, AnalyticFisher, GaussianMLPPolicy, LinearFeatureBaseline, NormalizedActions, _world, all_mean_, all_sum_, broadcast_initial_policy,
-                   flat_grad, flat_params, hidden_sizes_of, set_flat_params)
-from .vpg import _MEAN_ORDER, _two_layer_tanh, adam_step_, fused_adam_step_
+from ._lib import Kernels, available, ptr
+from .trpo import (TRPO, AnalyticFisher, FlatAdam, GaussianMLPPolicy, _MEAN_ORDER, _two_layer_tanh, _world, add_to_log_std_slot_, all_mean_, all_sum_,
+                   broadcast_initial_policy, flat_grad, flat_params, gaussian_policy_nets, hidden_sizes_of, make_cassie_algo, set_flat_params)
 
 
 # --------------------------------------------------------------------------------------------- the torch statements
@@ -90,13 +90,7 @@ def clipped_grad_closed_form(policy, obs, act, adv, old_mean, old_log_std, clip,
         std = policy.log_std.detach().exp()
         z = (act - mean) / std
         g = fisher.vjp(-scale * w * z / std)
-        g_ls = -scale * (w * (z * z - 1.0)).sum(0) - entropy_coeff
-        i0 = 0
-        for nm, p in policy.named_parameters():
-            if nm == "log_std":
-                g[i0:i0 + p.numel()] += g_ls.to(g.dtype)
-            i0 += p.numel()
-    return g
+        return add_to_log_std_slot_(policy, g, -scale * (w * (z * z - 1.0)).sum(0) - entropy_coeff)
 
 
 def aligned_flat_params(policy):
@@ -115,7 +109,7 @@ def aligned_flat_params(policy):
     return out
 
 
-class ClipGradKernels:
+class ClipGradKernels(Kernels):
     """The gradient of ppo_loss on minibatches of one batch, at the parameters in `theta` (a flat vector in parameter order that the caller
     updates in place: aligned_flat_params): width 32 -> CassieTrpoClipGrad, width 128 -> CassiePgClipGrad, one launch each; CPU tensors,
     other shapes, fused=False or a library without the symbols -> autograd of ppo_loss.  `kind`: "trpo_clip", "pg_clip" or "autograd"."""
@@ -129,24 +123,15 @@ class ClipGradKernels:
         if not fused or lin is None or not obs.is_cuda or obs.dtype != torch.float32 or theta.dtype != torch.float32:
             return
         hs = hidden_sizes_of(policy)
-        entry = {(32, 32): ("CassieTrpoClipGrad", "CassieTrpoClipGradRows", "CassieTrpoParamCount", "trpo_clip"),
-                 (128, 128): ("CassiePgClipGrad", "CassiePgClipGradRows", "CassiePgParamCount", "pg_clip")}.get(hs)
-        if entry is None:
+        prefix = {(32, 32): "CassieTrpo", (128, 128): "CassiePg"}.get(hs)
+        if prefix is None or not available(prefix + "ClipGrad"):
             return
-        import ctypes as ct
-        from . import _lib
-        try:
-            L = _lib.load()
-        except OSError:
-            return
-        if not hasattr(L, entry[0]):
-            return
+        super().__init__(obs.device, entry={k: prefix + k for k in ("ClipGrad", "ClipGradRows", "ParamCount")})
         D, A, H = lin[0].in_features, lin[2].out_features, hs[0]
-        NP = getattr(L, entry[2])(D, A)
+        NP = self.fn["ParamCount"](D, A)
         if NP == 0:
             return
-        self.L, self.ct, self.D, self.A, self.NP = L, ct, D, A, NP
-        self._entry, self._rows = getattr(L, entry[0]), getattr(L, entry[1])
+        self.D, self.A, self.NP = D, A, NP
         self.obs, self.act, self.adv, self.old_mean = obs.contiguous(), act.contiguous(), adv.to(torch.float32).contiguous(), old_mean.contiguous()
         # where every parameter sits in theta, and the permutation from a partial row [gW1 | gb1 | gW2 | gb2 | gW3 | gb3 | g_log_std] to it
         sizes = dict(zip(_MEAN_ORDER, [H * D, H, H * H, H, A * H, A]))
@@ -171,25 +156,25 @@ class ClipGradKernels:
             self.ent = torch.zeros(o, dtype=torch.float32, device=dev)
             self.ent[self.off["log_std"]:self.off["log_std"] + A] = -self.entropy_coeff
         self._bufs = {}
-        self.kind = entry[3]
+        self.kind = "trpo_clip" if H == 32 else "pg_clip"
+
+    def _rows(self, m):
+        return self.fn["ClipGradRows"](m)
 
     def _fused(self, idx, m, scale, stats_out):
-        ct, n = self.ct, self.obs.shape[0]
+        n = self.obs.shape[0]
         rows = self._rows(m)
         if rows not in self._bufs:
             self._bufs[rows] = (torch.empty((rows, self.NP + self.A), dtype=torch.float32, device=self.obs.device),
                                 torch.empty((rows, 3), dtype=torch.float64, device=self.obs.device))
         partial, stats = self._bufs[rows]
-        P = lambda t: ct.c_void_p(t.data_ptr())
+        P = ptr
         base = self.theta.data_ptr()
         W = [ct.c_void_p(base + 4 * self.off[k]) for k in _MEAN_ORDER]
         if idx is not None:
             assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == m
-        rc = self._entry(P(self.obs), n, self.D, self.A, *W, None if idx is None else P(idx), m, P(self.act), P(self.adv), P(self.old_mean), P(self.old_ls),
-                         ct.c_void_p(base + 4 * self.off["log_std"]), ct.c_float(self.clip), ct.c_float(scale), P(partial), P(stats),
-                         ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("%s failed (%d)" % (self._entry.__name__, rc))
+        self._call("ClipGrad", P(self.obs), n, self.D, self.A, *W, P(idx), m, P(self.act), P(self.adv), P(self.old_mean), P(self.old_ls),
+                   ct.c_void_p(base + 4 * self.off["log_std"]), ct.c_float(self.clip), ct.c_float(scale), P(partial), P(stats))
         g = partial.sum(0)[self.gather]
         if self.ent is not None:
             g += self.ent
@@ -217,21 +202,21 @@ class ClipGradKernels:
 
 
 # --------------------------------------------------------------------------------------------- PPO
-class PPO(TRPO):
+class PPO(FlatAdam, TRPO):
     """PPO on TRPO's sampler and baseline.  Switches (attributes, default True) that tests set to force the torch path: fused_policy_step,
     fused_gae (CassieTrpoGae), fused_grad (ClipGradKernels), fused_adam (CassiePgAdam).  last_grad_kind says which gradient ran."""
+    ALGO = "ppo"
 
     def __init__(self, env_step, env_reset, policy, baseline, n_envs, obs_dim, act_map, batch_size=10000, max_path_length=1000, discount=0.99,
                  learning_rate=3e-4, clip_range=0.2, gae_lambda=0.95, epochs=4, minibatch_size=None, entropy_coeff=0.0, beta1=0.9, beta2=0.999,
                  epsilon=1e-8, seed=1, env_reset_masked=None, env_id0=None):
         super().__init__(env_step, env_reset, policy, baseline, n_envs, obs_dim, act_map, batch_size=batch_size, max_path_length=max_path_length,
                          discount=discount, seed=seed, env_reset_masked=env_reset_masked, env_id0=env_id0)
-        self.learning_rate, self.beta1, self.beta2, self.epsilon = learning_rate, beta1, beta2, epsilon
+        self._adam_init(learning_rate, beta1, beta2, epsilon)
         self.clip_range, self.gae_lambda, self.epochs, self.entropy_coeff = clip_range, gae_lambda, int(epochs), entropy_coeff
         world, n_local = _world(), self.horizon * n_envs
         self.minibatch_size = n_local * world // 4 if minibatch_size is None else int(minibatch_size)
         self._check_minibatch(n_local)
-        self.adam_t, self.adam_m, self.adam_v = 0, None, None
         self.last_grad_kind = None
         dev = next(policy.parameters()).device
         rank = dist.get_rank() if dist.is_initialized() else 0
@@ -248,42 +233,19 @@ class PPO(TRPO):
                              % (n_local, m, self.minibatch_size, world))
         return m
 
-    @property
-    def hidden_sizes(self):
-        return hidden_sizes_of(self.policy)
-
-    def process(self, batch):
-        """TRPO.process with GAE(lambda) advantages: centring over ranks and the baseline fit follow it line by line."""
+    def _advantages(self, bk, batch, obs, tt):
+        """TRPO.process's hook with GAE(lambda) advantages: CassieTrpoGae, or gae_advantages on the values of the kernels or of the baseline."""
         T, N = batch["rew"].shape
-        flat = lambda x: x.reshape(T * N, *x.shape[2:])
-        obs, tt = flat(batch["obs"]), flat(batch["t"])
-        bk = self._baseline_kernels(obs)
         coeffs = self.baseline.coeffs
-        if bk is not None and getattr(self, "fused_gae", True):
+        self.last_gae_fused = bk is not None and getattr(self, "fused_gae", True)
+        if self.last_gae_fused:
             last_v = None if coeffs is None else bk.predict(self.obs.to(obs.dtype), self.path_t, coeffs)
-            returns, adv, sums = bk.gae(batch["obs"], batch["t"], batch["rew"], batch["done"], coeffs, last_v, self.discount, self.gae_lambda)
-            adv = flat(adv)
-            self.last_gae_fused = True
+            return bk.gae(batch["obs"], batch["t"], batch["rew"], batch["done"], coeffs, last_v, self.discount, self.gae_lambda)
+        if bk is not None and coeffs is not None:
+            last_v, values = bk.predict(self.obs.to(obs.dtype), self.path_t, coeffs), bk.predict(obs, tt, coeffs).view(T, N)
         else:
-            if bk is not None and coeffs is not None:
-                last_v, values = bk.predict(self.obs.to(obs.dtype), self.path_t, coeffs), bk.predict(obs, tt, coeffs).view(T, N)
-            else:
-                last_v, values = self.baseline.predict(self.obs.to(obs.dtype), self.path_t), self.baseline.predict(obs, tt).view(T, N)
-            returns, adv = gae_advantages(batch["rew"], batch["done"], values, last_v, self.discount, self.gae_lambda)
-            adv = flat(adv)
-            sums = torch.stack([adv.sum(), (adv * adv).sum()])
-            self.last_gae_fused = False
-        n = torch.tensor([adv.numel()], dtype=torch.float64, device=adv.device)
-        s12 = all_sum_(sums.clone(), "advantage_all_reduce"); n = all_sum_(n, "advantage_all_reduce")
-        mean = s12[0] / n
-        std = (s12[1] / n - mean * mean).clamp_min(0).sqrt()
-        adv = ((adv - mean) / (std + 1e-8)).to(obs.dtype)  # center_adv
-        if bk is not None:
-            A, b = bk.gram(obs, tt, flat(returns))
-            self.baseline.fit_normal_equations(A, b, bk.ridge_solve if getattr(self, "fused_solve", True) else None)
-        else:
-            self.baseline.fit(obs, tt, flat(returns))
-        return dict(obs=obs, act=flat(batch["act"]), mean=flat(batch["mean"]), log_std=flat(batch["log_std"]), adv=adv)
+            last_v, values = self.baseline.predict(self.obs.to(obs.dtype), self.path_t), self.baseline.predict(obs, tt).view(T, N)
+        return (*gae_advantages(batch["rew"], batch["done"], values, last_v, self.discount, self.gae_lambda), None)
 
     def optimize(self, d):
         pol = self.policy
@@ -294,11 +256,6 @@ class PPO(TRPO):
         theta = aligned_flat_params(pol)
         ck = ClipGradKernels(pol, theta, obs, act, adv, old_mean, old_lstd, self.clip_range, self.entropy_coeff, fused=getattr(self, "fused_grad", True))
         self.last_grad_kind = ck.kind
-        if self.adam_m is None:
-            self.adam_m, self.adam_v = torch.zeros_like(theta), torch.zeros_like(theta)
-        fused_adam = getattr(self, "fused_adam", True) and theta.is_cuda and theta.dtype == torch.float32
-        step = fused_adam_step_ if fused_adam else adam_step_
-        self.last_adam_fused = fused_adam
         # per minibatch step (loss sum, KL sum, clipped samples, gradient norm), kept on the device and read once behind the loop
         acc = torch.zeros((self.epochs * nmb, 4), dtype=torch.float64, device=obs.device)
         self.last_perms = []
@@ -312,8 +269,7 @@ class PPO(TRPO):
                 g, _ = ck.grad(idx, stats_out=acc[k, :3])
                 g = all_mean_(g.contiguous(), "gradient_all_reduce")
                 acc[k, 3] = torch.linalg.vector_norm(g, dtype=torch.float64)
-                self.adam_t += 1
-                step(theta, g.to(theta.dtype), self.adam_m, self.adam_v, self.adam_t, self.learning_rate, self.beta1, self.beta2, self.epsilon)
+                self.adam_step(theta, g.to(theta.dtype))
                 k += 1
         set_flat_params(pol, theta)
         M = float(m * world)
@@ -325,22 +281,13 @@ class PPO(TRPO):
 
     # ---- snapshot: TRPO's, plus the algorithm, the policy shape, the hyper-parameters, the Adam state and the permutation generator
     def _snapshot_fields(self):
-        return dict(algo="ppo", hidden_sizes=list(self.hidden_sizes), learning_rate=float(self.learning_rate), clip_range=float(self.clip_range),
-                    gae_lambda=float(self.gae_lambda), epochs=int(self.epochs), minibatch_size=int(self.minibatch_size), entropy_coeff=float(self.entropy_coeff),
-                    adam_t=int(self.adam_t), adam_m=None if self.adam_m is None else self.adam_m.detach().cpu(),
-                    adam_v=None if self.adam_v is None else self.adam_v.detach().cpu(), gen_mb_state=self.gen_mb.get_state())
+        return dict(super()._snapshot_fields(), learning_rate=float(self.learning_rate), clip_range=float(self.clip_range), gae_lambda=float(self.gae_lambda),
+                    epochs=int(self.epochs), minibatch_size=int(self.minibatch_size), entropy_coeff=float(self.entropy_coeff), **self._adam_snapshot(),
+                    gen_mb_state=self.gen_mb.get_state())
 
     def _load_fields(self, ck):
-        algo = ck.get("algo", "trpo")
-        if algo != "ppo":
-            raise ValueError("PPO.load: the snapshot was written by %s, this run is ppo" % algo)
-        theirs, mine = tuple(ck.get("hidden_sizes", (32, 32))), self.hidden_sizes
-        if theirs != mine:
-            raise ValueError("PPO.load: the snapshot's policy has hidden sizes %r, this run's has %r" % (theirs, mine))
-        dev = next(self.policy.parameters()).device
-        self.adam_t = int(ck.get("adam_t", 0))
-        self.adam_m = None if ck.get("adam_m") is None else ck["adam_m"].to(dev)
-        self.adam_v = None if ck.get("adam_v") is None else ck["adam_v"].to(dev)
+        super()._load_fields(ck)
+        self._adam_load(ck)
         if ck.get("gen_mb_state") is not None:
             self.gen_mb.set_state(ck["gen_mb_state"])
 
@@ -348,22 +295,5 @@ class PPO(TRPO):
 def make_cassie_ppo(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, hidden_sizes=(128, 128), init_std=1.0, terrain=None,
                     sync_policy=True, **kw):
     """PPO on the batched MI355X environment; the counterpart of vpg.make_cassie_vpg (same env, terrain and sync_policy rules)."""
-    from .vec_env import CassieVecEnv
-    env = CassieVecEnv(n_envs, kind=kind, control_mode=control_mode, n_substeps=10, auto_reset=True, device=device, trajectory=trajectory)
-    env.use_torch_stream()
-    dev = "cuda:%d" % device
-    bufs = env.alloc()
-    torch.manual_seed(seed)
-    obs_w = env.observation_space.shape[0]
-    policy = GaussianMLPPolicy(obs_w, env.adim, tuple(hidden_sizes), init_std=init_std).to(dev)
-    act_map = NormalizedActions(env.action_space.low, env.action_space.high, dev)
-    algo = PPO(lambda a: env.step(a, bufs), lambda: env.reset(bufs), policy, LinearFeatureBaseline(), n_envs, obs_w, act_map, seed=seed,
-               env_reset_masked=lambda m: env.reset(bufs, mask=m), **kw)
-    algo.env = env
-    algo.terrain_spec = terrain
-    if terrain is not None:
-        env.set_terrain_library(terrain_lib.library_of_spec(terrain), terrain_lib.DEFAULT_SIZE[:2])
-        env.set_terrain_ids(terrain_lib.assign_terrains(terrain["seed"], algo.env_ids, len(terrain["files"])).to(dev))
-    if sync_policy:
-        broadcast_initial_policy(algo)
-    return algo
+    return make_cassie_algo(PPO, gaussian_policy_nets(hidden_sizes, init_std), broadcast_initial_policy, n_envs, kind, control_mode, device, trajectory, seed,
+                            terrain, sync_policy, **kw)

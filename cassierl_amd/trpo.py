@@ -14,6 +14,7 @@ Multi-GPU: one process per GPU, each with its own shard of environments; the pol
 product, the baseline's normal equations and the line-search statistics are averaged with all_reduce (RCCL on MI355X, gloo in
 the CPU tests), so all ranks take the identical step.  Episode returns are gathered once per batch (rollout.gather_returns).
 """
+import ctypes as ct
 import math
 
 import torch
@@ -21,6 +22,7 @@ import torch.distributed as dist
 from torch import nn
 
 from . import terrain as terrain_lib
+from ._lib import Kernels, available, ptr
 
 
 # --------------------------------------------------------------------------------------------- distributed helpers
@@ -193,22 +195,24 @@ class LinearFeatureBaseline:
         return self.features(obs, t).double() @ self.coeffs
 
 
-class BaselineKernels:
+class BaselineKernels(Kernels):
     """LinearFeatureBaseline on the device batch as three HIP kernels (csrc/tu_trpo_baseline.hip, include/cassie_trpo.h): prediction,
     returns / advantages of the [T, n] batch in one pass, and the regression's normal equations on the FP64 matrix cores -- the feature
     matrix is never materialised.  CUDA float32 observations of a supported width only (ValueError otherwise: TRPO.process falls back to
     the torch expressions of LinearFeatureBaseline)."""
 
+    ENTRY = {k: "CassieTrpo" + k for k in ("BaselineFeatures", "GramRows", "GramRowSize", "BaselinePredict", "ReturnsAdvantages", "Gae", "BaselineGram",
+                                            "RidgeSolve")}
+
     def __init__(self, dev, obs_dim):
-        import ctypes as ct
-        from . import _lib
         if dev.type != "cuda":
             raise ValueError("BaselineKernels need a CUDA device")
-        self.L, self.ct, self.dev, self.D = _lib.load(), ct, dev, obs_dim
-        self.F = self.L.CassieTrpoBaselineFeatures(obs_dim)
+        super().__init__(dev)
+        self.D = obs_dim
+        self.F = self.fn["BaselineFeatures"](obs_dim)
         if self.F == 0:
             raise ValueError("BaselineKernels: unsupported observation width %d" % obs_dim)
-        rows, size = self.L.CassieTrpoGramRows(), self.L.CassieTrpoGramRowSize(obs_dim)
+        rows, size = self.fn["GramRows"](), self.fn["GramRowSize"](obs_dim)
         self.gram_partial = torch.empty((rows, size), dtype=torch.float64, device=dev)
         # full symmetric matrix from the upper 16 x 16 blocks (r <= c, r-major, each row-major): one gather
         nb = ((self.F + 1) + 15) // 16
@@ -225,55 +229,37 @@ class BaselineKernels:
         self.idx = idx.reshape(-1).to(dev)
         self.nz = 16 * nb
 
-    def _stream(self):
-        return self.ct.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-
-    def _p(self, t):
-        return self.ct.c_void_p(t.data_ptr()) if t is not None else None
-
     def predict(self, obs32, t, coeffs):
         m = obs32.shape[0]
         out = torch.empty(m, dtype=torch.float64, device=self.dev)
-        rc = self.L.CassieTrpoBaselinePredict(self._p(obs32.contiguous()), self._p(t.contiguous()), m, self.D, self._p(coeffs.contiguous()), self._p(out), self._stream())
-        if rc != 0:
-            raise RuntimeError("CassieTrpoBaselinePredict failed (%d)" % rc)
+        self._call("BaselinePredict", self._p(obs32.contiguous()), self._p(t.contiguous()), m, self.D, self._p(coeffs.contiguous()), self._p(out))
         return out
+
+    def _advantages(self, key, lam, obs_b, t_b, rew_b, cut_b, coeffs, last_value, gamma):
+        """The one body of returns_advantages (lam = (): CassieTrpoReturnsAdvantages) and gae (lam = (lambda,): CassieTrpoGae)."""
+        T, n = rew_b.shape
+        assert obs_b.is_contiguous() and t_b.is_contiguous() and rew_b.is_contiguous() and cut_b.is_contiguous()
+        assert obs_b.dtype == torch.float32 and t_b.dtype == torch.int64 and rew_b.dtype == torch.float64 and cut_b.dtype in (torch.bool, torch.uint8)
+        returns, adv = torch.empty_like(rew_b), torch.empty_like(rew_b)
+        partial = torch.empty(((n + 255) // 256, 2), dtype=torch.float64, device=self.dev)
+        self._call(key, self._p(obs_b), self._p(t_b), self._p(rew_b), self._p(cut_b), T, n, self.D,
+                   self._p(None if coeffs is None else coeffs.contiguous()), self._p(None if last_value is None else last_value.contiguous()),
+                   ct.c_double(gamma), *[ct.c_double(x) for x in lam], self._p(returns), self._p(adv), self._p(partial))
+        return returns, adv, partial.sum(0)
 
     def returns_advantages(self, obs_b, t_b, rew_b, cut_b, coeffs, last_value, gamma):
         """[T, n] batch -> returns [T, n], advantages [T, n] (float64) and (sum adv, sum adv^2) as a float64 pair on the device."""
-        T, n = rew_b.shape
-        assert obs_b.is_contiguous() and t_b.is_contiguous() and rew_b.is_contiguous() and cut_b.is_contiguous()
-        assert obs_b.dtype == torch.float32 and t_b.dtype == torch.int64 and rew_b.dtype == torch.float64 and cut_b.dtype in (torch.bool, torch.uint8)
-        returns, adv = torch.empty_like(rew_b), torch.empty_like(rew_b)
-        partial = torch.empty(((n + 255) // 256, 2), dtype=torch.float64, device=self.dev)
-        rc = self.L.CassieTrpoReturnsAdvantages(self._p(obs_b), self._p(t_b), self._p(rew_b), self._p(cut_b), T, n, self.D,
-                                                self._p(None if coeffs is None else coeffs.contiguous()), self._p(None if last_value is None else last_value.contiguous()),
-                                                self.ct.c_double(gamma), self._p(returns), self._p(adv), self._p(partial), self._stream())
-        if rc != 0:
-            raise RuntimeError("CassieTrpoReturnsAdvantages failed (%d)" % rc)
-        return returns, adv, partial.sum(0)
+        return self._advantages("ReturnsAdvantages", (), obs_b, t_b, rew_b, cut_b, coeffs, last_value, gamma)
 
     def gae(self, obs_b, t_b, rew_b, cut_b, coeffs, last_value, gamma, lam):
         """returns_advantages with GAE(lambda) advantages (CassieTrpoGae; cassierl_amd/ppo.py: gae_advantages is its torch statement)."""
-        T, n = rew_b.shape
-        assert obs_b.is_contiguous() and t_b.is_contiguous() and rew_b.is_contiguous() and cut_b.is_contiguous()
-        assert obs_b.dtype == torch.float32 and t_b.dtype == torch.int64 and rew_b.dtype == torch.float64 and cut_b.dtype in (torch.bool, torch.uint8)
-        returns, adv = torch.empty_like(rew_b), torch.empty_like(rew_b)
-        partial = torch.empty(((n + 255) // 256, 2), dtype=torch.float64, device=self.dev)
-        rc = self.L.CassieTrpoGae(self._p(obs_b), self._p(t_b), self._p(rew_b), self._p(cut_b), T, n, self.D,
-                                  self._p(None if coeffs is None else coeffs.contiguous()), self._p(None if last_value is None else last_value.contiguous()),
-                                  self.ct.c_double(gamma), self.ct.c_double(lam), self._p(returns), self._p(adv), self._p(partial), self._stream())
-        if rc != 0:
-            raise RuntimeError("CassieTrpoGae failed (%d)" % rc)
-        return returns, adv, partial.sum(0)
+        return self._advantages("Gae", (lam,), obs_b, t_b, rew_b, cut_b, coeffs, last_value, gamma)
 
     def gram(self, obs32, t, y):
         """(X'X [F, F], X'y [F]) of the baseline's features on m samples."""
         m = obs32.shape[0]
         assert obs32.is_contiguous() and t.is_contiguous() and y.is_contiguous() and y.dtype == torch.float64
-        rc = self.L.CassieTrpoBaselineGram(self._p(obs32), self._p(t), self._p(y), m, self.D, self._p(self.gram_partial), self._stream())
-        if rc != 0:
-            raise RuntimeError("CassieTrpoBaselineGram failed (%d)" % rc)
+        self._call("BaselineGram", self._p(obs32), self._p(t), self._p(y), m, self.D, self._p(self.gram_partial))
         G = self.gram_partial.sum(0)[self.idx].view(self.nz, self.nz)
         return G[:self.F, :self.F], G[:self.F, self.F]
 
@@ -281,9 +267,7 @@ class BaselineKernels:
         """(A + reg I)^-1 b on the device (Cholesky, with fit's retry rule inside the kernel: no read-back)."""
         A, b = A.contiguous(), b.contiguous()
         x = torch.empty_like(b)
-        rc = self.L.CassieTrpoRidgeSolve(self._p(A), self._p(b), A.shape[0], self.ct.c_double(reg), self._p(x), self._stream())
-        if rc != 0:
-            raise RuntimeError("CassieTrpoRidgeSolve failed (%d)" % rc)
+        self._call("RidgeSolve", self._p(A), self._p(b), A.shape[0], ct.c_double(reg), self._p(x))
         return x
 
 
@@ -329,6 +313,88 @@ def flat_grad(y, module, retain_graph=False, create_graph=False):
     return torch.cat([x.reshape(-1) for x in g])
 
 
+_MEAN_ORDER = ["mean_net.0.weight", "mean_net.0.bias", "mean_net.2.weight", "mean_net.2.bias", "mean_net.4.weight", "mean_net.4.bias"]   # the kernels' row order
+
+
+def _two_layer_tanh(policy):
+    """The three Linear layers of a two-hidden-layer tanh policy (what every policy kernel covers), else None."""
+    lin = [m for m in policy.mean_net if isinstance(m, nn.Linear)]
+    ok = len(lin) == 3 and all(isinstance(m, (nn.Linear, nn.Tanh)) for m in policy.mean_net)
+    return lin if ok else None
+
+
+def add_to_log_std_slot_(policy, g, g_ls):
+    """g (flat, parameter order) += g_ls in the log_std slot."""
+    i0 = 0
+    for nm, p in policy.named_parameters():
+        if nm == "log_std":
+            g[i0:i0 + p.numel()] += g_ls.to(g.dtype)
+        i0 += p.numel()
+    return g
+
+
+def closed_form_grad(policy, vjp, act, old_mean, old_lstd, adv):
+    """Gradient of -mean(logli(a | theta) adv) at theta = theta_old in closed form (the sampler's batch is on-policy): with z = (a - mean) / std,
+        d loss / d mean = -adv z / std / N,   d loss / d log_std = -sum_s adv (z^2 - 1) / N,
+    and the mean network's part J' (d loss / d mean) from `vjp` (a flat vector in parameter order with a zero log_std slot)."""
+    with torch.no_grad():
+        std = old_lstd.exp()
+        z = (act - old_mean) / std
+        n_inv = 1.0 / act.shape[0]
+        g = vjp(-(adv.unsqueeze(-1) * z / std) * n_inv)
+        g_ls = -((adv.unsqueeze(-1) * (z * z - 1.0)).sum(0)) * n_inv
+        return add_to_log_std_slot_(policy, g, g_ls)
+
+
+def adam_step_(theta, g, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+    """Lasagne's Adam on flat tensors, in place; t is the step count after its increment (the torch statement of CassiePgAdam).  The betas
+    are taken in the parameters' precision, as a float32 Lasagne graph holds them: for float32, 1 - 0.999f = 0.00099998713, not 0.001."""
+    beta1, beta2 = (torch.tensor([beta1, beta2], dtype=theta.dtype).tolist())
+    a = lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+    m.mul_(beta1).add_(g, alpha=1.0 - beta1)
+    v.mul_(beta2).addcmul_(g, g, value=1.0 - beta2)
+    theta.sub_(a * m / (v.sqrt() + eps))
+
+
+def fused_adam_step_(theta, g, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+    """adam_step_ as one launch of CassiePgAdam (contiguous float32 CUDA tensors)."""
+    k = Kernels(theta.device, entry={"Adam": "CassiePgAdam"})
+    for x in (theta, g, m, v):
+        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+            raise ValueError("CassiePgAdam needs contiguous float32 CUDA tensors")
+    P = ptr
+    k._call("Adam", theta.numel(), P(g), P(m), P(v), P(theta), int(t), ct.c_float(lr), ct.c_float(beta1), ct.c_float(beta2), ct.c_float(eps))
+
+
+class FlatAdam:
+    """Lasagne's Adam on the algorithm's flat parameter vector, for VPG, PPO and ES: the state (adam_t, adam_m, adam_v, attributes of the
+    algorithm and entries of its snapshot under these names), the step -- CassiePgAdam for float32 CUDA parameters unless the switch
+    `fused_adam` is off, else adam_step_; last_adam_fused says which -- and the state's way into and out of a snapshot."""
+
+    def _adam_init(self, learning_rate, beta1, beta2, epsilon):
+        self.learning_rate, self.beta1, self.beta2, self.epsilon = learning_rate, beta1, beta2, epsilon
+        self.adam_t, self.adam_m, self.adam_v = 0, None, None
+        self.last_adam_fused = None
+
+    def adam_step(self, theta, g):
+        """One step of theta (flat, contiguous, updated in place) along g."""
+        if self.adam_m is None:
+            self.adam_m, self.adam_v = torch.zeros_like(theta), torch.zeros_like(theta)
+        self.adam_t += 1
+        fused = self.last_adam_fused = getattr(self, "fused_adam", True) and theta.is_cuda and theta.dtype == torch.float32
+        (fused_adam_step_ if fused else adam_step_)(theta, g, self.adam_m, self.adam_v, self.adam_t, self.learning_rate, self.beta1, self.beta2, self.epsilon)
+
+    def _adam_snapshot(self):
+        return dict(adam_t=int(self.adam_t), adam_m=None if self.adam_m is None else self.adam_m.detach().cpu(),
+                    adam_v=None if self.adam_v is None else self.adam_v.detach().cpu())
+
+    def _adam_load(self, ck):
+        dev = next(self.policy.parameters()).device
+        self.adam_t = int(ck.get("adam_t", 0))
+        self.adam_m = None if ck.get("adam_m") is None else ck["adam_m"].to(dev)
+        self.adam_v = None if ck.get("adam_v") is None else ck["adam_v"].to(dev)
+
+
 def conjugate_gradient(Avp, b, iters=10, tol=1e-10):
     """rllab/misc/krylov.py:cg -- including its early exit on the residual, but WITHOUT asking the device for it: once
     r.r < tol the step length is zero from then on (x and r stay what they were at the break), so no iteration waits for a
@@ -358,9 +424,8 @@ class AnalyticFisher:
     kind = "analytic"
 
     def __init__(self, policy, obs, eps=1e-8):
-        lin = [m for m in policy.mean_net if isinstance(m, nn.Linear)]
-        act_ok = all(isinstance(m, (nn.Linear, nn.Tanh)) for m in policy.mean_net)
-        if len(lin) != 3 or not act_ok:
+        lin = _two_layer_tanh(policy)
+        if lin is None:
             raise ValueError("AnalyticFisher covers the two-hidden-layer tanh policy of trpo_cassie.py only")
         self.names = [n for n, _ in policy.named_parameters()]
         self.shapes = [tuple(p.shape) for p in policy.parameters()]
@@ -413,35 +478,33 @@ class AnalyticFisher:
         return self._reverse(w, torch.zeros_like(self.h_ls))
 
 
-class FusedFisher:
+class FusedFisher(Kernels):
     """The same Fisher-vector products as AnalyticFisher, each in ONE launch of the fused HIP kernel (csrc/tu_trpo.hip,
     include/cassie_trpo.h): forward mode along the direction, precision of the old Gaussian, reverse mode and the outer-product
     accumulation per wavefront; obs is the only per-sample tensor read.  `vjp(w)` gives J' w for per-sample cotangents (the policy
     gradient).  CUDA float32 policies of the supported shapes only (ValueError otherwise: the caller falls back to AnalyticFisher).
-    PgFisher is the same object for the 128 x 128 policy: it swaps the entry points (_bind) and the hidden width."""
+    PgFisher is the same object for the 128 x 128 policy: it swaps the entry points (ENTRY) and the hidden width."""
     kind, hidden = "trpo_fvp", 32
+    ENTRY = dict(ParamCount="CassieTrpoParamCount", PartialRows="CassieTrpoPartialRows", SurrogateRows="CassieTrpoPartialRows", Fvp="CassieTrpoFvp",
+                 Vjp="CassieTrpoVjp", Surrogate="CassieTrpoSurrogate", CgUpdate="CassieTrpoCgUpdate")
 
     def __init__(self, policy, obs, eps=1e-8):
-        import ctypes as ct
-        from . import _lib
         name, H = type(self).__name__, self.hidden
-        lin = [m for m in policy.mean_net if isinstance(m, nn.Linear)]
-        if len(lin) != 3 or not all(isinstance(m, (nn.Linear, nn.Tanh)) for m in policy.mean_net):
+        lin = _two_layer_tanh(policy)
+        if lin is None:
             raise ValueError("%s covers the two-hidden-layer tanh policy of trpo_cassie.py only" % name)
         if not obs.is_cuda or obs.dtype != torch.float32 or lin[0].out_features != H or lin[1].out_features != H:
             raise ValueError("%s needs a float32 CUDA batch and %d x %d hidden units" % (name, H, H))
-        self.L = _lib.load()
-        self._bind()
+        super().__init__(obs.device)
         self.D, self.A = lin[0].in_features, lin[2].out_features
-        self.NP = self._param_count(self.D, self.A)
+        self.NP = self.fn["ParamCount"](self.D, self.A)
         if self.NP == 0:
             raise ValueError("%s: unsupported policy shape %d -> %d" % (name, self.D, self.A))
-        self.ct = ct
         self.obs = obs.contiguous()
         self.n = obs.shape[0]
         self.names = [n for n, _ in policy.named_parameters()]
         self.shapes = [tuple(p.shape) for p in policy.parameters()]
-        self.order = ["mean_net.0.weight", "mean_net.0.bias", "mean_net.2.weight", "mean_net.2.bias", "mean_net.4.weight", "mean_net.4.bias"]
+        self.order = _MEAN_ORDER
         with torch.no_grad():
             self.theta = {n: p.detach().clone().contiguous() for n, p in policy.named_parameters()}
             var = (2 * policy.log_std.detach()).exp()
@@ -452,18 +515,13 @@ class FusedFisher:
         # offsets of the kernel's row layout [gW1 | gb1 | gW2 | gb2 | gW3 | gb3]
         self.sizes = [H * self.D, H, H * H, H, self.A * H, self.A]
 
-    def _bind(self):
-        """The width-32 entry points (csrc/tu_trpo.hip)."""
-        L = self.L
-        self._param_count, self._partial_rows, self._sur_rows = L.CassieTrpoParamCount, L.CassieTrpoPartialRows, L.CassieTrpoPartialRows
-        self._vjp_entry, self._sur_entry, self._cg_entry = L.CassieTrpoVjp, L.CassieTrpoSurrogate, L.CassieTrpoCgUpdate
+    def _partial_rows(self, n):
+        return self.fn["PartialRows"](n)
 
-    def _fvp(self, parts, stream):
+    def _fvp(self, parts):
         """The mean network's F v for this rank's samples into self.partial (one row per wavefront)."""
-        rc = self.L.CassieTrpoFvp(self.ct.c_void_p(self.obs.data_ptr()), self.n, self.D, self.A, *self._ptrs(self.theta), *self._ptrs(parts),
-                                  self.ct.c_void_p(self.prec.data_ptr()), self.ct.c_float(1.0 / self.n), self.ct.c_void_p(self.partial.data_ptr()), stream)
-        if rc != 0:
-            raise RuntimeError("CassieTrpoFvp failed (%d)" % rc)
+        self._call("Fvp", self._p(self.obs), self.n, self.D, self.A, *self._ptrs(self.theta), *self._ptrs(parts), self._p(self.prec), ct.c_float(1.0 / self.n),
+                   self._p(self.partial))
 
     def _split(self, v):
         parts, i = {}, 0
@@ -481,20 +539,19 @@ class FusedFisher:
         return torch.cat([pieces[n].reshape(-1) for n in self.names])
 
     def _ptrs(self, d):
-        return [self.ct.c_void_p(d[n].data_ptr()) for n in self.order]
+        return [self._p(d[n]) for n in self.order]
 
     @torch.no_grad()
     def __call__(self, v):
         v = v.to(torch.float32).contiguous()
         parts = self._split(v)
-        self._fvp(parts, self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream))
+        self._fvp(parts)
         return self._assemble(self.partial.sum(0), self.h_ls * parts["log_std"])
 
     @torch.no_grad()
     def mean_product(self, v):
         """The mean network's part of F v for this rank's samples, [NP] float32 in the kernel's order (no log_std block, no damping)."""
-        parts = self._split(v)
-        self._fvp(parts, self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream))
+        self._fvp(self._split(v))
         return self.partial.sum(0)
 
     @torch.no_grad()
@@ -514,24 +571,17 @@ class FusedFisher:
         r, p = b.clone(), b.clone()
         scal = torch.stack([r @ r, torch.ones((), dtype=b.dtype, device=b.device)]).contiguous()
         hls = self.h_ls.to(torch.float32).contiguous()
-        P = lambda t: self.ct.c_void_p(t.data_ptr())
+        P = self._p
         for _ in range(iters):
             apm = all_mean_(self.mean_product(p), "fvp_all_reduce")
-            rc = self._cg_entry(n, ls_off, self.A, P(apm), P(hls), self.ct.c_float(reg), self.ct.c_float(tol), P(x), P(r), P(p), P(scal),
-                                self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream))
-            if rc != 0:
-                raise RuntimeError("%s failed (%d)" % (self._cg_entry.__name__, rc))
+            self._call("CgUpdate", n, ls_off, self.A, P(apm), P(hls), ct.c_float(reg), ct.c_float(tol), P(x), P(r), P(p), P(scal))
         return x
 
     @torch.no_grad()
     def vjp(self, w):
         """J' w for w [n, act_dim] float32 (cotangents on the mean); the log_std slot of the result is zero."""
         w = w.to(torch.float32).contiguous()
-        stream = self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream)
-        rc = self._vjp_entry(self.ct.c_void_p(self.obs.data_ptr()), self.n, self.D, self.A, *self._ptrs(self.theta),
-                             self.ct.c_void_p(w.data_ptr()), self.ct.c_void_p(self.partial.data_ptr()), stream)
-        if rc != 0:
-            raise RuntimeError("%s failed (%d)" % (self._vjp_entry.__name__, rc))
+        self._call("Vjp", self._p(self.obs), self.n, self.D, self.A, *self._ptrs(self.theta), self._p(w), self._p(self.partial))
         return self._assemble(self.partial.sum(0), torch.zeros_like(self.theta["log_std"]))
 
     @torch.no_grad()
@@ -540,15 +590,12 @@ class FusedFisher:
         the line search's evaluation.  old_log_std: the [act_dim] vector of the state-independent old log-std.  Two float64 scalars on the device."""
         live = dict(policy.named_parameters())
         if not hasattr(self, "_sur"):
-            self._sur = torch.empty((self._sur_rows(self.n), 2), dtype=torch.float64, device=self.obs.device)
-        P = lambda t: self.ct.c_void_p(t.data_ptr())
+            self._sur = torch.empty((self.fn["SurrogateRows"](self.n), 2), dtype=torch.float64, device=self.obs.device)
+        P = self._p
         act, adv, old_mean = act.contiguous(), adv.to(torch.float32).contiguous(), old_mean.contiguous()
         old_ls = old_log_std.to(torch.float32).contiguous()
-        stream = self.ct.c_void_p(torch.cuda.current_stream(self.obs.device).cuda_stream)
-        rc = self._sur_entry(P(self.obs), self.n, self.D, self.A, *[P(live[k].detach()) for k in self.order], P(live["log_std"].detach()), P(old_ls),
-                             P(act), P(adv), P(old_mean), P(self._sur), stream)
-        if rc != 0:
-            raise RuntimeError("%s failed (%d)" % (self._sur_entry.__name__, rc))
+        self._call("Surrogate", P(self.obs), self.n, self.D, self.A, *[P(live[k].detach()) for k in self.order], P(live["log_std"].detach()), P(old_ls),
+                   P(act), P(adv), P(old_mean), P(self._sur))
         s = self._sur.sum(0) / self.n
         return s[0], s[1]
 
@@ -557,23 +604,16 @@ class PgFisher(FusedFisher):
     """FusedFisher for the 128 x 128 policy (csrc/tu_pg_trpo.hip): the product is CassiePgFvp (forward mode into a [n, act_dim] cotangent,
     then CassiePgVjp), the CG step CassiePgCgUpdate, the line search CassiePgSurrogate and the gradient CassiePgVjp.  Same interface."""
     kind, hidden = "pg_fvp", 128
+    ENTRY = {k: "CassiePg" + k for k in ("ParamCount", "PartialRows", "SurrogateRows", "Fvp", "Vjp", "Surrogate", "CgUpdate")}
 
-    def _bind(self):
-        L = self.L
-        self._param_count, self._partial_rows, self._sur_rows = L.CassiePgParamCount, L.CassiePgPartialRows, L.CassiePgSurrogateRows
-        self._vjp_entry, self._sur_entry, self._cg_entry = L.CassiePgVjp, L.CassiePgSurrogate, L.CassiePgCgUpdate
-
-    def _fvp(self, parts, stream):
+    def _fvp(self, parts):
         if not hasattr(self, "_work"):
             self._work = torch.empty((self.n, self.A), dtype=torch.float32, device=self.obs.device)
         # the kernel reads db1, dW2, db2, dW3 as float4: in the flat parameter vector they sit behind log_std (act_dim floats), so the
         # direction's mean-network part is copied into a fresh buffer, where every block starts on a 16-byte boundary
         direction = dict(zip(self.order, torch.split(torch.cat([parts[k].reshape(-1) for k in self.order]), self.sizes)))
-        rc = self.L.CassiePgFvp(self.ct.c_void_p(self.obs.data_ptr()), self.n, self.D, self.A, *self._ptrs(self.theta), *self._ptrs(direction),
-                                self.ct.c_void_p(self.prec.data_ptr()), self.ct.c_float(1.0 / self.n), self.ct.c_void_p(self._work.data_ptr()),
-                                self.ct.c_void_p(self.partial.data_ptr()), stream)
-        if rc != 0:
-            raise RuntimeError("CassiePgFvp failed (%d)" % rc)
+        self._call("Fvp", self._p(self.obs), self.n, self.D, self.A, *self._ptrs(self.theta), *self._ptrs(direction), self._p(self.prec),
+                   ct.c_float(1.0 / self.n), self._p(self._work), self._p(self.partial))
 
 
 # --------------------------------------------------------------------------------------------- TRPO
@@ -624,63 +664,45 @@ class TRPO:
         (the torch operations below)."""
         if not getattr(self, "fused_policy_step", True) or dev.type != "cuda" or pol_dtype != torch.float32 or not isinstance(self.act_map, NormalizedActions):
             return None
-        lin = [m for m in self.policy.mean_net if isinstance(m, nn.Linear)]
-        if len(lin) != 3 or not all(isinstance(m, (nn.Linear, nn.Tanh)) for m in self.policy.mean_net):
+        lin = _two_layer_tanh(self.policy)
+        if lin is None:
             return None
         D, A = lin[0].in_features, lin[2].out_features
         entry = {(32, 32): "CassieTrpoPolicyStep", (128, 128): "CassiePgPolicyStep"}.get((lin[0].out_features, lin[1].out_features))
-        if (D, A) not in ((26, 6), (26, 7)) or entry is None or self.obs_dim != D:
-            return None
-        try:
-            import ctypes as ct
-            from . import _lib
-            L = _lib.load()
-        except OSError:
+        if (D, A) not in ((26, 6), (26, 7)) or entry is None or self.obs_dim != D or not available():
             return None
         if not hasattr(self, "_env_actions") or self._env_actions.shape != (self.n_envs, A):
             self._env_actions = torch.empty((self.n_envs, A), dtype=torch.float64, device=dev)
-        P = lambda t: ct.c_void_p(t.data_ptr())
+        P = ptr
         w = [P(lin[0].weight), P(lin[0].bias), P(lin[1].weight), P(lin[1].bias), P(lin[2].weight), P(lin[2].bias), P(self.policy.log_std)]
         low, high, n = self.act_map.low, self.act_map.high, self.n_envs
         # the kernel reads the bounds as `const double*`: anything else (NormalizedActions takes a dtype) goes the torch way
         if not all(t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == A for t in (low, high)):
             return None
-
-        fn = getattr(L, entry)
+        k = Kernels(dev, entry={"PolicyStep": entry})
         self.policy_step_entry = entry
 
         def step(obs, noise, obs32, mean, act):
             if obs.dtype != torch.float64 or not obs.is_contiguous():
                 raise TypeError("%s: observations must be a contiguous float64 tensor (got %s)" % (entry, obs.dtype))
             assert noise.is_contiguous() and obs32.is_contiguous()
-            rc = fn(P(obs), n, D, A, *w, P(noise), P(low), P(high), P(obs32), P(mean), P(act), P(self._env_actions),
-                    ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if rc != 0:
-                raise RuntimeError("%s failed (%d)" % (entry, rc))
+            k._call("PolicyStep", P(obs), n, D, A, *w, P(noise), P(low), P(high), P(obs32), P(mean), P(act), P(self._env_actions))
         return step
 
     def _fused_sampler_step(self, dev):
         """The sampler's per-step bookkeeping as one launch (include/cassie_trpo.h: CassieTrpoSamplerStep), or None."""
-        if not getattr(self, "fused_sampler_step", True) or dev.type != "cuda":
+        if not getattr(self, "fused_sampler_step", True) or dev.type != "cuda" or not available():
             return None
-        try:
-            import ctypes as ct
-            from . import _lib
-            L = _lib.load()
-        except OSError:
-            return None
-        n = self.n_envs
-        if not hasattr(self, "_book_partial") or self._book_partial.shape[0] != L.CassieTrpoSamplerRows(n):
-            self._book_partial = torch.empty((L.CassieTrpoSamplerRows(n), 2), dtype=torch.float64, device=dev)
-        P = lambda t: ct.c_void_p(t.data_ptr())
+        k = Kernels(dev, entry={"Rows": "CassieTrpoSamplerRows", "Step": "CassieTrpoSamplerStep"})
+        n, P = self.n_envs, ptr
+        if not hasattr(self, "_book_partial") or self._book_partial.shape[0] != k.fn["Rows"](n):
+            self._book_partial = torch.empty((k.fn["Rows"](n), 2), dtype=torch.float64, device=dev)
 
         def book(rew, done, rew_row, t_row, cut_row):
             assert rew.is_contiguous() and done.is_contiguous() and rew_row.is_contiguous() and t_row.is_contiguous() and cut_row.is_contiguous()
             assert self.path_t.dtype == torch.int64 and self.path_ret.dtype == torch.float64
-            rc = L.CassieTrpoSamplerStep(P(rew), P(done), n, ct.c_longlong(int(self.max_path_length)), P(self.path_t), P(self.path_ret), P(rew_row), P(t_row),
-                                         P(cut_row), P(self._book_partial), ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if rc != 0:
-                raise RuntimeError("CassieTrpoSamplerStep failed (%d)" % rc)
+            k._call("Step", P(rew), P(done), n, ct.c_longlong(int(self.max_path_length)), P(self.path_t), P(self.path_ret), P(rew_row), P(t_row), P(cut_row),
+                    P(self._book_partial))
         return book
 
     def _book_step(self, book, rew, done, rew_row, t_row, cut_row, ep):
@@ -767,37 +789,40 @@ class TRPO:
             self._bk = bk
         return bk
 
+    def _advantages(self, bk, batch, obs, tt):
+        """process()'s hook: (returns [T, N], advantages [T, N], [sum adv, sum adv^2] or None for process to take them) of the batch.  bk: the
+        BaselineKernels or None (the torch statements); obs, tt: the flat views.  TRPO: gae_lambda = 1; unfinished paths are bootstrapped
+        with the baseline of the next observation (0 at iteration 0)."""
+        T, N = batch["rew"].shape
+        if bk is not None:
+            # value of every sample, return-to-go and advantage in one pass over the batch (csrc/tu_trpo_baseline.hip)
+            coeffs = self.baseline.coeffs
+            last_v = None if coeffs is None else bk.predict(self.obs.to(obs.dtype), self.path_t, coeffs)
+            return bk.returns_advantages(batch["obs"], batch["t"], batch["rew"], batch["done"], coeffs, last_v, self.discount)
+        last_v = self.baseline.predict(self.obs.to(obs.dtype), self.path_t)
+        returns = discounted_returns(batch["rew"], batch["done"], self.discount, last_v)
+        return returns, returns - self.baseline.predict(obs, tt).view(T, N), None
+
     def process(self, batch):
         T, N = batch["rew"].shape
         flat = lambda x: x.reshape(T * N, *x.shape[2:])
         obs, tt = flat(batch["obs"]), flat(batch["t"])
         bk = self._baseline_kernels(obs)
+        returns, adv, sums = self._advantages(bk, batch, obs, tt)
+        adv = flat(adv)
+        if sums is None:
+            sums = torch.stack([adv.sum(), (adv * adv).sum()])
+        n = torch.tensor([adv.numel()], dtype=torch.float64, device=adv.device)
+        s12 = all_sum_(sums.clone(), "advantage_all_reduce"); n = all_sum_(n, "advantage_all_reduce")
+        mean = s12[0] / n
+        std = (s12[1] / n - mean * mean).clamp_min(0).sqrt()
+        adv = ((adv - mean) / (std + 1e-8)).to(obs.dtype)  # center_adv
         if bk is not None:
-            # value of every sample, return-to-go and advantage in one pass over the batch, the regression's normal equations on the
-            # FP64 matrix cores (csrc/tu_trpo_baseline.hip): no feature matrix in memory
-            coeffs = self.baseline.coeffs
-            last_v = None if coeffs is None else bk.predict(self.obs.to(obs.dtype), self.path_t, coeffs)
-            returns, adv, sums = bk.returns_advantages(batch["obs"], batch["t"], batch["rew"], batch["done"], coeffs, last_v, self.discount)
-            adv = flat(adv)
-            n = torch.tensor([adv.numel()], dtype=torch.float64, device=adv.device)
-            s12 = all_sum_(sums.clone(), "advantage_all_reduce"); n = all_sum_(n, "advantage_all_reduce")
-            mean = s12[0] / n
-            std = (s12[1] / n - mean * mean).clamp_min(0).sqrt()
-            adv = ((adv - mean) / (std + 1e-8)).to(obs.dtype)  # center_adv
+            # the regression's normal equations on the FP64 matrix cores: no feature matrix in memory
             A, b = bk.gram(obs, tt, flat(returns))
             self.baseline.fit_normal_equations(A, b, bk.ridge_solve if getattr(self, "fused_solve", True) else None)
-            return dict(obs=obs, act=flat(batch["act"]), mean=flat(batch["mean"]), log_std=flat(batch["log_std"]), adv=adv)
-        # bootstrap unfinished paths with the baseline of the next observation (0 at iteration 0)
-        last_v = self.baseline.predict(self.obs.to(obs.dtype), self.path_t)
-        returns = discounted_returns(batch["rew"], batch["done"], self.discount, last_v)
-        values = self.baseline.predict(obs, tt).view(T, N)
-        adv = flat(returns - values)                       # gae_lambda = 1
-        n = torch.tensor([adv.numel()], dtype=torch.float64, device=adv.device)
-        s1 = all_sum_(adv.sum().view(1).clone(), "advantage_all_reduce"); s2 = all_sum_((adv * adv).sum().view(1).clone(), "advantage_all_reduce"); n = all_sum_(n, "advantage_all_reduce")
-        mean = s1 / n
-        std = (s2 / n - mean * mean).clamp_min(0).sqrt()
-        adv = ((adv - mean) / (std + 1e-8)).to(obs.dtype)  # center_adv
-        self.baseline.fit(obs, tt, flat(returns))
+        else:
+            self.baseline.fit(obs, tt, flat(returns))
         return dict(obs=obs, act=flat(batch["act"]), mean=flat(batch["mean"]), log_std=flat(batch["log_std"]), adv=adv)
 
     # ---- constrained update
@@ -830,24 +855,13 @@ class TRPO:
                     fisher = None
         self.last_fisher_kind = "autograd" if fisher is None else fisher.kind
         if fisher is not None:
-            # policy gradient in closed form too: at theta = theta_old the likelihood ratio is 1, so with z = (a - mean) / std
-            #   d loss / d mean = -adv z / std / N,   d loss / d log_std = -sum_s adv (z^2 - 1) / N,   loss = -mean(adv)
-            # and J' (d loss / d mean) comes from the Fisher object's reverse pass (r04: 3.9 ms of autograd -> 0.5 ms at 524 288 samples).
+            # policy gradient in closed form too (closed_form_grad): at theta = theta_old the likelihood ratio is 1, loss = -mean(adv), and
+            # J' (d loss / d mean) comes from the Fisher object's reverse pass (r04: 3.9 ms of autograd -> 0.5 ms at 524 288 samples).
             # ASSUMES the batch is exactly on-policy -- old_mean / old_lstd were produced by the CURRENT parameters (true for this
             # sampler: optimize() runs right after the rollout that recorded them) -- and a state-independent log_std; a caller that
             # reuses an older batch must set analytic_fisher = False (the autograd gradient below makes neither assumption).
-            with torch.no_grad():
-                std = old_lstd.exp()
-                z = (act - old_mean) / std
-                n_inv = 1.0 / obs.shape[0]
-                g = fisher.vjp(-(adv.unsqueeze(-1) * z / std) * n_inv)
-                g_ls = -((adv.unsqueeze(-1) * (z * z - 1.0)).sum(0)) * n_inv
-                i0 = 0
-                for nm, p_ in pol.named_parameters():
-                    if nm == "log_std":
-                        g[i0:i0 + p_.numel()] += g_ls.to(g.dtype)
-                    i0 += p_.numel()
-                loss = -adv.mean()
+            g = closed_form_grad(pol, fisher.vjp, act, old_mean, old_lstd, adv)
+            loss = -adv.mean()
             g = all_mean_(g, "gradient_all_reduce")
         else:
             loss, _ = surrogate()
@@ -946,18 +960,28 @@ class TRPO:
         torch.save(ck, mine + ".tmp")
         os.replace(mine + ".tmp", mine)
 
+    ALGO = "trpo"   # the snapshot's "algo" entry (a plain TRPO snapshot has none)
+
+    @property
+    def hidden_sizes(self):
+        return hidden_sizes_of(self.policy)
+
     def _snapshot_fields(self):
-        """Entries of the snapshot beyond the common ones (a subclass adds its optimiser state): TRPO records the policy's hidden sizes."""
-        return dict(hidden_sizes=list(hidden_sizes_of(self.policy)))
+        """Entries of the snapshot beyond the common ones: the algorithm (but for TRPO itself) and the policy's hidden sizes; a subclass adds
+        its hyper-parameters and optimiser state."""
+        return dict({} if self.ALGO == "trpo" else dict(algo=self.ALGO), hidden_sizes=list(self.hidden_sizes))
 
     def _load_fields(self, ck):
         """Called with the loaded snapshot before anything is restored: refuses a snapshot that is not this run's (a subclass also takes
-        back its _snapshot_fields()).  TRPO: the policy's hidden sizes must match (a snapshot without them was written by a 32 x 32 run)."""
-        if ck.get("algo") in ("ddpg", "sac", "td3"):   # their "policy" is a deterministic / squashed-Gaussian actor, not a GaussianMLPPolicy
-            raise ValueError("TRPO.load: the snapshot was written by %s, this run is trpo" % ck["algo"])
-        theirs, mine = tuple(ck.get("hidden_sizes", (32, 32))), hidden_sizes_of(self.policy)
+        back its _snapshot_fields()).  A plain TRPO run continues any GaussianMLPPolicy snapshot (its own, VPG's, PPO's, ES's) but not the
+        deterministic / squashed-Gaussian actors of ddpg, sac and td3; every other algorithm takes back only its own.  The policy's hidden
+        sizes must match (a snapshot without them was written by a 32 x 32 run)."""
+        name, algo = type(self).__name__, ck.get("algo", "trpo")
+        if algo != self.ALGO and (self.ALGO != "trpo" or algo in ("ddpg", "sac", "td3")):
+            raise ValueError("%s.load: the snapshot was written by %s, this run is %s" % (name, algo, self.ALGO))
+        theirs, mine = tuple(ck.get("hidden_sizes", (32, 32))), self.hidden_sizes
         if theirs != mine:
-            raise ValueError("TRPO.load: the snapshot's policy has hidden sizes %r, this run's has %r" % (theirs, mine))
+            raise ValueError("%s.load: the snapshot's policy has hidden sizes %r, this run's has %r" % (name, theirs, mine))
 
     def load(self, path, restore_sampler=True):
         """Returns (extra, sampler_restored): policy / baseline / iteration always come back; the sampler state (env records,
@@ -1004,29 +1028,43 @@ def broadcast_initial_policy(algo):
         set_flat_params(algo.policy, theta)
 
 
-def make_cassie_trpo(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, sync_policy=True, terrain=None, hidden_sizes=(32, 32),
-                     init_std=2.0, **kw):
-    """trpo_cassie.py:12-42 on the batched MI355X environment.  sync_policy=False: NOTHING collective happens in here (the env, its workspaces, the
-    policy are local allocations that can fail on one rank alone); the caller agrees on success across ranks first and then calls
-    broadcast_initial_policy(algo) (bench.py's TRPO stage).  terrain: None (the flat floor) or a spec of terrain.terrain_spec -- every
-    environment on its own field of the spec's library, drawn by terrain.assign_terrains over the GLOBAL env ids; snapshots record it.
-    hidden_sizes / init_std: the policy (trpo_cassie.py's 32 x 32 and 2.0 by default; (128, 128) runs on the kernels of csrc/tu_pg*.hip)."""
+def make_cassie_algo(cls, make_nets, broadcast, n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, terrain=None, sync_policy=True,
+                     terrain_ids=None, **kw):
+    """cls on the batched MI355X environment: what every make_cassie_* is.  make_nets(obs_dim, act_dim, dev) -> the constructor's arguments between
+    env_reset and n_envs (the policy first), built right after torch.manual_seed(seed): every rank builds the same initial networks, and with
+    sync_policy `broadcast(algo)` makes rank 0's authoritative anyway.  sync_policy=False: NOTHING collective happens in here (the env, its
+    workspaces, the networks are local allocations that can fail on one rank alone); the caller agrees on success across ranks first and then
+    broadcasts (bench.py's TRPO stage).  terrain: None (the flat floor) or a spec of terrain.terrain_spec -- every environment on its own field of
+    the spec's library, drawn by terrain.assign_terrains over terrain_ids(the GLOBAL env ids) (default: the ids themselves); snapshots record it."""
     from .vec_env import CassieVecEnv
     env = CassieVecEnv(n_envs, kind=kind, control_mode=control_mode, n_substeps=10, auto_reset=True, device=device, trajectory=trajectory)
     env.use_torch_stream()
     dev = "cuda:%d" % device
     bufs = env.alloc()
-    torch.manual_seed(seed)  # trpo_cassie.py:53 seed=1: every rank builds the same initial policy ...
-    obs_w = env.observation_space.shape[0]  # what step() emits (26 for both kinds); the policy is sized from the env, as trpo_cassie.py does through env.spec
-    policy = GaussianMLPPolicy(obs_w, env.adim, tuple(hidden_sizes), init_std=init_std).to(dev)
+    torch.manual_seed(seed)  # trpo_cassie.py:53 seed=1
+    obs_w = env.observation_space.shape[0]  # what step() emits (26 for both kinds); the networks are sized from the env, as trpo_cassie.py does through env.spec
+    nets = make_nets(obs_w, env.adim, dev)
     act_map = NormalizedActions(env.action_space.low, env.action_space.high, dev)
-    algo = TRPO(lambda a: env.step(a, bufs), lambda: env.reset(bufs), policy, LinearFeatureBaseline(), n_envs, obs_w, act_map, seed=seed,
-                env_reset_masked=lambda m: env.reset(bufs, mask=m), **kw)
+    algo = cls(lambda a: env.step(a, bufs), lambda: env.reset(bufs), *nets, n_envs, obs_w, act_map, seed=seed, env_reset_masked=lambda m: env.reset(bufs, mask=m), **kw)
     algo.env = env
     algo.terrain_spec = terrain
     if terrain is not None:
+        ids = algo.env_ids if terrain_ids is None else terrain_ids(algo.env_ids)
         env.set_terrain_library(terrain_lib.library_of_spec(terrain), terrain_lib.DEFAULT_SIZE[:2])
-        env.set_terrain_ids(terrain_lib.assign_terrains(terrain["seed"], algo.env_ids, len(terrain["files"])).to(dev))
-    if sync_policy:   # ... and rank 0's parameters are authoritative anyway
-        broadcast_initial_policy(algo)
+        env.set_terrain_ids(terrain_lib.assign_terrains(terrain["seed"], ids, len(terrain["files"])).to(dev))
+    if sync_policy:
+        broadcast(algo)
     return algo
+
+
+def gaussian_policy_nets(hidden_sizes, init_std):
+    """make_nets of the on-policy family: a GaussianMLPPolicy and a LinearFeatureBaseline."""
+    return lambda obs_dim, act_dim, dev: (GaussianMLPPolicy(obs_dim, act_dim, tuple(hidden_sizes), init_std=init_std).to(dev), LinearFeatureBaseline())
+
+
+def make_cassie_trpo(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, sync_policy=True, terrain=None, hidden_sizes=(32, 32),
+                     init_std=2.0, **kw):
+    """trpo_cassie.py:12-42 on the batched MI355X environment (make_cassie_algo: env, terrain and sync_policy rules).  hidden_sizes / init_std: the
+    policy (trpo_cassie.py's 32 x 32 and 2.0 by default; (128, 128) runs on the kernels of csrc/tu_pg*.hip)."""
+    return make_cassie_algo(TRPO, gaussian_policy_nets(hidden_sizes, init_std), broadcast_initial_policy, n_envs, kind, control_mode, device, trajectory, seed,
+                            terrain, sync_policy, **kw)
