@@ -43,6 +43,7 @@ EXPORTS = [
     "CassieTrpoGae", "CassieTrpoClipGradRows", "CassieTrpoClipGrad", "CassiePgClipGradRows", "CassiePgClipGrad",
     # ES (include/cassie_trpo.h)
     "CassieEsParamCount", "CassieEsPairsPerWorkgroup", "CassieEsPolicyStep", "CassieEsBook", "CassieEsGradRows", "CassieEsGrad",
+    "CassieEsWideParamCount", "CassieEsWidePairsPerWorkgroup", "CassieEsWidePolicyStep",
 ]
 
 

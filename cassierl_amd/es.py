@@ -2,18 +2,18 @@
 for a whole episode, nothing is stored per step, and the update is one weighted sum of noise vectors.
 
 There is no reference counterpart (rllab ships the family as CEM / CMA-ES and no script of the reference uses it): the torch statements in this
-module are the specification, the kernels of csrc/tu_es.hip evaluate them.
+module are the specification, the kernels of csrc/tu_es.hip (and, for the 128 x 128 policy's step, csrc/tu_es_wide.hip) evaluate them.
 
   parameters  theta = flat_params(policy.mean_net), the row [W1 | b1 | W2 | b2 | W3 | b3] (vpg._MEAN_ORDER, the actor row of csrc/mlp32_tiles.h),
-              P entries: 2118 for the shape (26, 6), 2151 for (26, 7), 1863 for (17, 7).  log_std is never touched, so a TRPO run can load an ES
-              snapshot and continue from it.
+              P entries: 2118 for the shape (26, 6), 2151 for (26, 7), 1863 for (17, 7) at 32 x 32 hidden units; 20 742, 20 871 and 19 719 at
+              128 x 128 (19 590 for (17, 6)).  log_std is never touched, so a TRPO run can load an ES snapshot and continue from it.
   noise       table = randn(table_size) float32 on the device from a generator seeded by table_seed (default 1 << 24 entries, 64 MB): regenerated
               from the seed on load, never written to a snapshot.
   population  n_envs (even) per rank; local environment i evaluates direction d = i >> 1 with sign s = +1 (i even) or -1 (i odd), direction d is
               eps_d = table[off_d : off_d + P].  The offsets of ALL ranks are drawn once per iteration, randint(0, table_size - P + 1, (M_global,)),
               from a generator seeded identically on every rank; a rank keeps its shard (TRPO's rule for the exploration noise: a run does not
               depend on how the environments are sharded).
-  action      (es_actions_torch; CassieEsPolicyStep)  w_i = theta + (s_i sigma) eps_(i >> 1);  mean_i = W3 tanh(W2 tanh(W1 obs_i + b1) + b2) + b3
+  action      (es_actions_torch; CassieEsPolicyStep, CassieEsWidePolicyStep at width 128)  w_i = theta + (s_i sigma) eps_(i >> 1);  mean_i = W3 tanh(W2 tanh(W1 obs_i + b1) + b2) + b3
               with the layers cut out of w_i;  act_i = alive_i ? mean_i : 0;  env_action_i = NormalizedActions(act_i): a dead environment gets
               the middle of the box.
   rollout     reset every environment, then up to max_path_length steps with (es_book_torch; CassieEsBook)
@@ -26,8 +26,9 @@ module are the specification, the kernels of csrc/tu_es.hip evaluate them.
               descent direction -g + l2_coeff theta, one Lasagne Adam step (vpg.adam_step_ / CassiePgAdam).
 
 Defaults are OpenAI's: sigma 0.02, learning_rate 0.01, l2_coeff 0.005; max_path_length 1000.  The snapshot machinery and the gather are TRPO's
-(cassierl_amd/trpo.py), unchanged.  Only the 32 x 32 policy in float32 on the GPU has kernels; other hidden sizes, CPU tensors, float64 or a library
-without the symbols take the torch statements.
+(cassierl_amd/trpo.py), unchanged.  The 32 x 32 and the 128 x 128 policy in float32 on the GPU have kernels (the policy step is one kernel per width;
+the bookkeeping, the gradient and Adam do not see the width); other hidden sizes, CPU tensors, float64 or a library without the symbols -- one
+without the CassieEsWide* symbols at width 128 only -- take the torch statements.
 """
 import ctypes as ct
 import time
@@ -112,15 +113,30 @@ def pair_weights(u):
 
 # --------------------------------------------------------------------------------------------- the kernel-call layer
 class EsKernels(Kernels):
-    """The library calls of ES on one noise table (csrc/tu_es.hip).  ENTRY names the exported functions; every call goes through the dict `fn` (key ->
-    function, looked up at call time, so a test can wrap its entries).  The kernels do not check offsets: set_directions does, on the host, with
-    one read-back, and raises before anything is launched.  ValueError for an unsupported shape or a table that is not a contiguous float32 vector."""
+    """The library calls of ES on one noise table (csrc/tu_es.hip, csrc/tu_es_wide.hip).  ENTRY names the exported functions; every call goes through
+    the dict `fn` (key -> function, looked up at call time, so a test can wrap its entries).  `hidden` = (128, 128) puts the Wide* functions under
+    the keys ParamCount, PairsPerWorkgroup and PolicyStep (entry_for); an object looks up the symbols of its own width only.  The kernels do not
+    check offsets: set_directions does, on the host, with one read-back, and raises before anything is launched.  ValueError for an unsupported
+    shape or width, or a table that is not a contiguous float32 vector."""
 
     ENTRY = {"ParamCount": "CassieEsParamCount", "PairsPerWorkgroup": "CassieEsPairsPerWorkgroup", "PolicyStep": "CassieEsPolicyStep", "Book": "CassieEsBook",
-             "GradRows": "CassieEsGradRows", "Grad": "CassieEsGrad"}
+             "GradRows": "CassieEsGradRows", "Grad": "CassieEsGrad",
+             "WideParamCount": "CassieEsWideParamCount", "WidePairsPerWorkgroup": "CassieEsWidePairsPerWorkgroup", "WidePolicyStep": "CassieEsWidePolicyStep"}
 
-    def __init__(self, table, n_envs, obs_dim, act_dim, low=None, high=None):
-        super().__init__(table.device)
+    @classmethod
+    def entry_for(cls, hidden):
+        """key -> exported name for the policy width `hidden`: (32, 32) or (128, 128)."""
+        hidden = tuple(int(x) for x in hidden)
+        entry = {k: v for k, v in cls.ENTRY.items() if not k.startswith("Wide")}
+        if hidden == (128, 128):
+            entry.update({k[4:]: v for k, v in cls.ENTRY.items() if k.startswith("Wide")})
+        elif hidden != (32, 32):
+            raise ValueError("EsKernels: hidden sizes %r have no kernels (32 x 32 and 128 x 128 do)" % (hidden,))
+        return entry
+
+    def __init__(self, table, n_envs, obs_dim, act_dim, low=None, high=None, hidden=(32, 32)):
+        super().__init__(table.device, entry=self.entry_for(hidden))
+        self.hidden = tuple(int(x) for x in hidden)
         self.D, self.A, self.n = int(obs_dim), int(act_dim), int(n_envs)
         self.P = self.fn["ParamCount"](self.D, self.A)
         if self.P == 0:
@@ -154,7 +170,8 @@ class EsKernels(Kernels):
         self.offsets, self._dir_np = offsets, n_params
 
     def policy_step(self, obs, theta, sigma, alive=None, out=None):
-        """env_actions [n, act_dim] float64 of the population at obs [n, obs_dim] float64 (CassieEsPolicyStep); alive uint8 [n] or None."""
+        """env_actions [n, act_dim] float64 of the population at obs [n, obs_dim] float64 (CassieEsPolicyStep or CassieEsWidePolicyStep); alive
+        uint8 [n] or None."""
         if self.offsets is None or self._dir_np != self.P:
             raise ValueError("EsKernels.policy_step: set_directions first")
         if obs.dtype != torch.float64 or not obs.is_contiguous() or obs.shape != (self.n, self.D) or obs.device != self.dev:
@@ -210,7 +227,7 @@ def make_table(size, seed, device):
 class ES(FlatAdam, TRPO):
     """ES on TRPO's snapshot machinery and gather; the baseline is unused.  Switches (attributes, default True) that tests set to force the torch
     statements: fused_policy_step (CassieEsPolicyStep), fused_book (CassieEsBook), fused_grad (CassieEsGrad), fused_adam (CassiePgAdam).
-    last_policy_step_kind ("es_step" / "torch"), last_book_fused, last_grad_kind ("es_grad" / "torch") and last_adam_fused say what ran."""
+    last_policy_step_kind ("es_step" / "es_wide_step" at width 128 / "torch"), last_book_fused, last_grad_kind ("es_grad" / "torch") and last_adam_fused say what ran."""
     ALGO = "es"
 
     def __init__(self, env_step, env_reset, policy, baseline, n_envs, obs_dim, act_map, sigma=0.02, learning_rate=0.01, l2_coeff=0.005, max_path_length=1000,
@@ -238,24 +255,25 @@ class ES(FlatAdam, TRPO):
         self.last_policy_step_kind = self.last_grad_kind = self.last_book_fused = None
 
     def _kernels(self):
-        """EsKernels for this run when they apply -- CUDA, a float32 two-layer tanh policy with 32 x 32 hidden units of a supported shape, rllab's
-        normalize() action map with float64 bounds -- else None (the torch statements)."""
+        """EsKernels for this run when they apply -- CUDA, a float32 two-layer tanh policy with 32 x 32 or 128 x 128 hidden units of a supported shape,
+        rllab's normalize() action map with float64 bounds -- else None (the torch statements)."""
         if self._ek is not None:
             return self._ek or None
         self._ek = False
         p = next(self.policy.parameters())
         lin = _two_layer_tanh(self.policy)
-        if p.device.type != "cuda" or p.dtype != torch.float32 or lin is None or self.hidden_sizes != (32, 32) or not isinstance(self.act_map, NormalizedActions):
+        if p.device.type != "cuda" or p.dtype != torch.float32 or lin is None or self.hidden_sizes not in ((32, 32), (128, 128)) or not isinstance(self.act_map, NormalizedActions):
             return None
         low, high = self.act_map.low, self.act_map.high
         A = lin[2].out_features
         if lin[0].in_features != self.obs_dim or not all(t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == A for t in (low, high)):
             return None
         # no library, one without the symbols or an unsupported shape: the torch statements.  Anything else EsKernels objects to is a mistake and raises.
-        if not available(*EsKernels.ENTRY.values()) or Kernels(p.device, entry={"ParamCount": "CassieEsParamCount"}).fn["ParamCount"](self.obs_dim, A) == 0:
+        entry = EsKernels.entry_for(self.hidden_sizes)   # (the symbols of this width only: a library without the wide ones still serves 32 x 32)
+        if not available(*entry.values()) or Kernels(p.device, entry={"ParamCount": entry["ParamCount"]}).fn["ParamCount"](self.obs_dim, A) == 0:
             return None
         self._ek = None   # (a refusal below is raised again by the next call, not remembered as 'torch')
-        self._ek = EsKernels(self.table, self.n_envs, self.obs_dim, A, low, high)
+        self._ek = EsKernels(self.table, self.n_envs, self.obs_dim, A, low, high, hidden=self.hidden_sizes)
         return self._ek
 
     def draw_directions(self):
@@ -284,7 +302,7 @@ class ES(FlatAdam, TRPO):
         alive = torch.ones(n, dtype=torch.uint8, device=dev)
         step_fused = ek is not None and getattr(self, "fused_policy_step", True)
         book_fused = ek is not None and getattr(self, "fused_book", True)
-        self.last_policy_step_kind, self.last_book_fused = "es_step" if step_fused else "torch", False
+        self.last_policy_step_kind, self.last_book_fused = ("es_wide_step" if ek.hidden == (128, 128) else "es_step") if step_fused else "torch", False
         for t in range(self.max_path_length):
             if step_fused:
                 actions = ek.policy_step(obs, theta, self.sigma, alive)

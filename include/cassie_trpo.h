@@ -315,6 +315,15 @@ int CassieEsPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, c
                        const long long* offsets_dev, float sigma, const unsigned char* alive_dev, const double* low_dev, const double* high_dev,
                        double* env_actions_dev, void* stream);
 
+/* The same three for the 128 x 128 tanh mean network (csrc/tu_es_wide.hip): P = 128 D + 128 + 128 * 128 + 128 + 128 A + A for the shapes above
+ * (20 742 for (26, 6)), 0 for any other shape; CassieEsWidePolicyStep has CassieEsPolicyStep's arguments, contract and return codes, with this P.
+ * The pair's slice of the table is streamed in chunks through LDS, every entry read once; CassieEsBook and CassieEsGrad serve both widths. */
+int CassieEsWideParamCount(int obs_dim, int act_dim);
+int CassieEsWidePairsPerWorkgroup(void);
+int CassieEsWidePolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* theta_dev, const float* table_dev, long long table_len,
+                           const long long* offsets_dev, float sigma, const unsigned char* alive_dev, const double* low_dev, const double* high_dev,
+                           double* env_actions_dev, void* stream);
+
 /* Bookkeeping of one Env.step of the population in one launch, with rew / done as CassieVecStep wrote them:
  *   fitness[i] += alive[i] ? rew[i] : 0;  length[i] += alive[i];  alive[i] &= !done[i]   (alive: one byte, 0 / 1). */
 int CassieEsBook(const double* rew_dev, const unsigned char* done_dev, int n, unsigned char* alive_dev, double* fitness_dev, long long* length_dev, void* stream);

@@ -2,7 +2,7 @@
 """Evolution strategy (cassierl_amd/es.py) on the batched MI355X environment; runs under torchrun exactly as train_vpg.py does
 (`python -m torch.distributed.run --nproc-per-node 8 train_es.py --envs-per-gpu 65536`).
 
-Every environment runs its own perturbed copy of the 32 x 32 policy for one episode (two environments per direction, antithetic); an iteration
+Every environment runs its own perturbed copy of the policy (--hidden: 32,32 or 128,128 on the kernels) for one episode (two environments per direction, antithetic); an iteration
 is one rollout of up to --max-path-length steps and one Adam step on the weighted sum of the directions.  Defaults are OpenAI's.
 """
 import argparse
@@ -31,7 +31,7 @@ def main():
     ap.add_argument("--terrain-elevation", type=float, default=1.0, help="height of a white pixel in metres (the <hfield> size_z)")
     ap.add_argument("--terrain-seed", type=int, default=1, help="seed of the file draw and of the per-pair field ids")
     ap.add_argument("--dump-params", default="", help="rank 0 writes the flat policy parameters (.npy) after the last iteration")
-    ap.add_argument("--hidden", default="32,32", help="hidden layer widths of the policy (only 32,32 runs on the kernels)")
+    ap.add_argument("--hidden", default="32,32", help="hidden layer widths of the policy (32,32 and 128,128 run on the kernels, any other on the torch statements)")
     ap.add_argument("--sigma", type=float, default=0.02, help="standard deviation of the parameter perturbations")
     ap.add_argument("--learning-rate", type=float, default=0.01, help="Adam step size")
     ap.add_argument("--l2-coeff", type=float, default=0.005, help="weight decay added to the descent direction")
