@@ -1,13 +1,19 @@
 // cassie_pg_net.h -- device code shared by the width-128 policy units (tu_pg.hip: policy step, J' w, Adam; tu_pg_trpo.hip: Fisher-vector
-// product, line search, CG step): the shapes, the weight pointers, and the forward pass of one tile of 32 samples in the accumulator layout.
-// Read tu_pg.hip's header for the layout.
+// product, line search, CG step; tu_ppo.hip: clipped-surrogate gradient): the shapes, the forward pass of one tile of 32 samples in the
+// accumulator layout, the per-wavefront LDS transposes of the VJP (wave_put, wave_get).  The VJP's reverse pass of a group of four tiles and
+// the workgroup's row store are cassie_pg_vjp.inc and cassie_pg_vjp_row.inc (shared as text: see there).  The layout primitives (v16f, TILE_MFMA, Net, tanh_fast, zero16,
+// row_of, bias_tile) are cassie_tiles.h's.  Read tu_pg.hip's header for the layout.
 #ifndef CASSIE_PG_NET_H_
 #define CASSIE_PG_NET_H_
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cassie_tiles.h"
+
 namespace cassie_pg {
+
+using namespace cassie_tiles;
 
 constexpr int H = 128;            // hidden units (both layers)
 constexpr int NB = H / 32;        // 32-row blocks of a hidden layer
@@ -20,42 +26,13 @@ template <int D, int A> struct Shape {
   static constexpr int O_W1 = 0, O_B1 = H * D, O_W2 = O_B1 + H, O_B2 = O_W2 + H * H, O_W3 = O_B2 + H, O_B3 = O_W3 + A * H;
 };
 
-struct Net { const float *W1, *b1, *W2, *b2, *W3, *b3; };
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-#define PG_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
-// tanh through the hardware exp2 / rcp, as in tu_trpo.hip: 1 - 2 / (e^2x + 1)
-__device__ __forceinline__ float tanh_fast(float x) {
-  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
-}
-
-__device__ __forceinline__ v16f zero16() {
-  v16f z;
-#pragma unroll
-  for (int v = 0; v < 16; v++) z[v] = 0.0f;
-  return z;
-}
-
-// C operand: b[r(v, h)] in register v (rows 8 g + 4 h .. + 3 are one float4)
-__device__ __forceinline__ v16f bias_tile(const float* __restrict__ b, int h) {
-  v16f z;
-#pragma unroll
-  for (int g = 0; g < 4; g++) {
-    const float4 x = *reinterpret_cast<const float4*>(b + 8 * g + 4 * h);
-    z[4 * g] = x.x; z[4 * g + 1] = x.y; z[4 * g + 2] = x.z; z[4 * g + 3] = x.w;
-  }
-  return z;
-}
-
 // y += W[row0 + c][col0 + r(v, h)] x[v] over the 16 k-steps (W row-major with ld floats per row; col0 and ld multiples of 4)
 __device__ __forceinline__ void gemm_block(const float* __restrict__ W, int ld, int row0, int col0, bool on, const v16f& x, v16f& y, int c, int h) {
 #pragma unroll
   for (int g = 0; g < 4; g++) {
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (on) a = *reinterpret_cast<const float4*>(W + (size_t)(row0 + c) * ld + col0 + 8 * g + 4 * h);
-    y = PG_MFMA(a.x, x[4 * g], y); y = PG_MFMA(a.y, x[4 * g + 1], y); y = PG_MFMA(a.z, x[4 * g + 2], y); y = PG_MFMA(a.w, x[4 * g + 3], y);
+    y = TILE_MFMA(a.x, x[4 * g], y); y = TILE_MFMA(a.y, x[4 * g + 1], y); y = TILE_MFMA(a.z, x[4 * g + 2], y); y = TILE_MFMA(a.w, x[4 * g + 3], y);
   }
 }
 
@@ -70,7 +47,7 @@ __device__ __forceinline__ void forward_hidden(const Net& th, const float (&xb)[
     for (int s = 0; s < KS1; s++) {
       const int k = 2 * s + h;
       const float a = k < D ? th.W1[(32 * ob + c) * D + k] : 0.0f;
-      y = PG_MFMA(a, xb[s], y);
+      y = TILE_MFMA(a, xb[s], y);
     }
 #pragma unroll
     for (int v = 0; v < 16; v++) y[v] = tanh_fast(y[v]);
@@ -87,7 +64,25 @@ __device__ __forceinline__ void forward_hidden(const Net& th, const float (&xb)[
   }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// ---------------------------------------------------------------------------------------------------------------- VJP (tu_pg.hip, tu_ppo.hip)
+__device__ __forceinline__ void wave_put(float* __restrict__ t, const v16f (&x)[NB], int c, int h) {   // accumulator layout -> [row][sample]
+#pragma unroll
+  for (int b = 0; b < NB; b++)
+#pragma unroll
+    for (int v = 0; v < 16; v++) t[ROW_AT(32 * b, v, h) * TP + c] = x[b][v];
+}
+__device__ __forceinline__ void wave_get(const float* __restrict__ t, float (&y)[16], int c, int h) {   // lane (c, h): row c, samples 16 h .. 16 h + 15
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const float4 b = *reinterpret_cast<const float4*>(&t[c * TP + 16 * h + 4 * q]);
+    y[4 * q] = b.x; y[4 * q + 1] = b.y; y[4 * q + 2] = b.z; y[4 * q + 3] = b.w;
+  }
+}
+
+inline int vjp_blocks(int n) {   // groups of four tiles, one workgroup per CU at the most
+  const int groups = ((n + 31) / 32 + WAVES - 1) / WAVES;
+  return groups < 1 ? 1 : (groups > MAX_VJP_BLOCKS ? MAX_VJP_BLOCKS : groups);
+}
 
 }  // namespace cassie_pg
 

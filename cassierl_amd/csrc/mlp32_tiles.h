@@ -1,19 +1,19 @@
 // mlp32_tiles.h -- what the kernels of the 32 x 32 ReLU networks share (tu_ddpg.hip, tu_sac.hip, tu_td3.hip): the shapes of a parameter row, the
-// A-operand images of every matrix product (laid out once per workgroup in LDS), the accumulator-layout helpers, the per-wavefront LDS
-// transposes, the fixed-order reduction of the wavefronts' rows, the live critic's tile pass of the twin-critic kernels and the Adam / soft-update
-// body of the apply kernels.  The layout is tu_trpo.hip's (read its header first): exact float32
-// v_mfma_f32_32x32x2_f32, a tile of 32 samples per wavefront, sample on the lane c = lane & 31, hidden unit r(v, h) = (v & 3) + 8 (v >> 2) + 4 h
-// in register v of the lane half h.
+// fixed-order reduction of the wavefronts' rows, the live critic's tile pass of the twin-critic kernels and the Adam / soft-update body of the
+// apply kernels.  The layout is tu_trpo.hip's (read its header first).  The accumulator-layout primitives, the A-operand images of every matrix
+// product (laid out once per workgroup in LDS) and the per-wavefront LDS transposes are cassie_tiles.h's, shared with the tanh policies.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "cassie_tiles.h"
+
 namespace cassie_mlp32 {
 
-constexpr int H = 32;
-constexpr int TP = 36;            // floats per row of a transpose tile (tu_trpo.hip)
-constexpr int WAVES = 4;
+using namespace cassie_tiles;
+using namespace cassie_tiles::w32;   // H, TP, WAVES, Kind, wel, Grp, fill_images, aop, put, get
+
 constexpr int MAX_BLOCKS = 256;   // one workgroup per CU; one partial row per workgroup
 
 template <int D, int A> struct Shape {
@@ -26,95 +26,9 @@ template <int D, int A> struct Shape {
   static constexpr int Q_W1 = 0, Q_B1 = H * D, Q_W2 = Q_B1 + H, Q_B2 = Q_W2 + H * HA, Q_W3 = Q_B2 + H, Q_B3 = Q_W3 + H;
 };
 
-struct Net { const float *W1, *b1, *W2, *b2, *W3, *b3; };
 struct NetRW { float *W1, *b1, *W2, *b2, *W3, *b3; };
 struct Pool { const float *obs, *act, *rew, *term, *nobs; long long cap; };
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-#define DDPG_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ float tanh_fast(float x) {   // tu_trpo.hip: 1 - 2 / (e^2x + 1), absolute error ~1e-7
-  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
-}
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ int row_of(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
-
-// Element `st` (k-step) of the A operand of a product for lane (c, h): see tu_trpo.hip's header for why W[c][r(st, h)] is what k-step st
-// of Y = W X needs when X sits in the accumulator layout.
-enum Kind {
-  K_FIRST,   // first layer, W [32][D]: k = 2 st + h
-  K_HID,     // W [32][32] on an activation
-  K_HIDQ,    // the critic's W2 [32][32 + A], hidden columns
-  K_OUT,     // the actor's W3 [A][32] padded to 32 rows
-  K_HIDT,    // W [32][32] transposed (reverse mode)
-  K_HIDQT,   // the critic's W2 hidden columns transposed
-  K_ACTIN,   // the critic's W2 action columns: k-step st < 4 sums over action a = st + 4 h
-  K_W3T,     // the actor's W3 transposed: cotangent row a = st + 4 h, st < 4
-  K_DA,      // the critic's W2 action columns transposed, padded to 32 rows: dQ/da = W2a' G2
-  K_HEAD,    // a two-headed actor's W3 [2 A][32], rows permuted by head_row and padded to 32 (tu_sac.hip)
-  K_HEADT    // that W3 transposed: cotangent row head_row(r(st, h)), st < 8
-};
-// row of a two-headed output layer (mean [0, A), log_std [A, 2 A)) that image row i of the output tile holds: mean a on image row a, log_std a on
-// image row 8 + a (a < A <= 8), -1 for a padding row
-template <int A> __device__ __forceinline__ int head_row(int i) { return i < 8 ? (i < A ? i : -1) : (i < 16 && i - 8 < A ? A + i - 8 : -1); }
-template <int D, int A> __device__ __forceinline__ float wel(int kind, const float* __restrict__ W, int st, int c, int h) {
-  constexpr int HA = H + A, KS1 = (D + 1) / 2;
-  const int r = row_of(st, h);
-  switch (kind) {
-    case K_FIRST: { const int k = 2 * st + h; return (st < KS1 && k < D) ? W[c * D + k] : 0.0f; }
-    case K_HID: return W[c * H + r];
-    case K_HIDQ: return W[c * HA + r];
-    case K_OUT: return c < A ? W[c * H + r] : 0.0f;
-    case K_HIDT: return W[r * H + c];
-    case K_HIDQT: return W[r * HA + c];
-    case K_ACTIN: { const int a = st + 4 * h; return (st < 4 && a < A) ? W[c * HA + H + a] : 0.0f; }
-    case K_W3T: { const int a = st + 4 * h; return (st < 4 && a < A) ? W[a * H + c] : 0.0f; }
-    case K_HEAD: { const int o = head_row<A>(c); return o >= 0 ? W[o * H + r] : 0.0f; }
-    case K_HEADT: { const int o = st < 8 ? head_row<A>(r) : -1; return o >= 0 ? W[o * H + c] : 0.0f; }
-    default: return c < A ? W[r * HA + H + c] : 0.0f;   // K_DA
-  }
-}
-struct Grp { int kind; const float* W; int q0, nq; };
-
-template <int D, int A, int NG> __device__ __forceinline__ void fill_images(float4 (*wimg)[64], const Grp (&g)[NG], int wave, int lane) {
-  const int c = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int k = 0; k < NG; k++) {
-    for (int q = wave; q < g[k].nq; q += WAVES) {
-      float v4[4];
-#pragma unroll
-      for (int e = 0; e < 4; e++) v4[e] = wel<D, A>(g[k].kind, g[k].W, 4 * q + e, c, h);
-      wimg[g[k].q0 + q][lane] = make_float4(v4[0], v4[1], v4[2], v4[3]);
-    }
-  }
-}
-__device__ __forceinline__ void aop(const float4 (*wimg)[64], int q0, int lane, float (&a)[16]) {   // the 16 k-steps of a product
-#pragma unroll
-  for (int q = 0; q < 4; q++) { const float4 w = wimg[q0 + q][lane]; a[4 * q] = w.x; a[4 * q + 1] = w.y; a[4 * q + 2] = w.z; a[4 * q + 3] = w.w; }
-}
-__device__ __forceinline__ v16f bias_tile(const float* sb, int h) {   // C operand: bias[r(v, h)] in register v
-  v16f z;
-#pragma unroll
-  for (int g = 0; g < 4; g++) {
-    const float4 b = *reinterpret_cast<const float4*>(&sb[8 * g + 4 * h]);
-    z[4 * g] = b.x; z[4 * g + 1] = b.y; z[4 * g + 2] = b.z; z[4 * g + 3] = b.w;
-  }
-  return z;
-}
-__device__ __forceinline__ void put(float* t, const v16f& x, int c, int h) {   // accumulator layout -> [row][sample] image
-#pragma unroll
-  for (int v = 0; v < 16; v++) t[row_of(v, h) * TP + c] = x[v];
-}
-__device__ __forceinline__ void get(const float* t, float (&y)[16], int c, int h) {   // lane (i = c, h): row i, samples 16 h .. 16 h + 15
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const float4 b = *reinterpret_cast<const float4*>(&t[c * TP + 16 * h + 4 * q]);
-    y[4 * q] = b.x; y[4 * q + 1] = b.y; y[4 * q + 2] = b.z; y[4 * q + 3] = b.w;
-  }
-}
 __device__ __forceinline__ void relu16(v16f& x) {
 #pragma unroll
   for (int v = 0; v < 16; v++) x[v] = x[v] > 0.0f ? x[v] : 0.0f;
@@ -129,17 +43,17 @@ template <int KS1> __device__ __forceinline__ void two_layers(const float4 (*wim
   h1 = bias_tile(sb1, h);
   aop(wimg, qW1, lane, aw);
 #pragma unroll
-  for (int s = 0; s < KS1; s++) h1 = DDPG_MFMA(aw[s], xb[s], h1);
+  for (int s = 0; s < KS1; s++) h1 = TILE_MFMA(aw[s], xb[s], h1);
   relu16(h1);
   z2 = bias_tile(sb2, h);
   aop(wimg, qW2, lane, aw);
 #pragma unroll
-  for (int v = 0; v < 16; v++) z2 = DDPG_MFMA(aw[v], h1[v], z2);
+  for (int v = 0; v < 16; v++) z2 = TILE_MFMA(aw[v], h1[v], z2);
 }
 // + W2[:, 32:] a for the action a = v + 4 h in register v < 4 (one quad of k-steps)
 __device__ __forceinline__ void add_action(const float4 (*wimg)[64], int qA, int lane, const float (&ab)[4], v16f& z2) {
   const float4 w = wimg[qA][lane];
-  z2 = DDPG_MFMA(w.x, ab[0], z2); z2 = DDPG_MFMA(w.y, ab[1], z2); z2 = DDPG_MFMA(w.z, ab[2], z2); z2 = DDPG_MFMA(w.w, ab[3], z2);
+  z2 = TILE_MFMA(w.x, ab[0], z2); z2 = TILE_MFMA(w.y, ab[1], z2); z2 = TILE_MFMA(w.z, ab[2], z2); z2 = TILE_MFMA(w.w, ab[3], z2);
 }
 // q = b3 + W3 . h2 for the sample of this lane (both halves of the wavefront hold the result)
 __device__ __forceinline__ float q_head(const float (&w3)[16], float b3, const v16f& h2) {
@@ -189,7 +103,7 @@ __device__ __forceinline__ void critic_step(const float4 (*wimg)[64], int q0, co
   float aw[16], ta_[16], tb_[16];
   aop(wimg, q0 + LQ_W2T, lane, aw);
 #pragma unroll
-  for (int v = 0; v < 16; v++) g1 = DDPG_MFMA(aw[v], g2[v], g1);
+  for (int v = 0; v < 16; v++) g1 = TILE_MFMA(aw[v], g2[v], g1);
 #pragma unroll
   for (int v = 0; v < 16; v++) g1[v] = c1[v] > 0.0f ? g1[v] : 0.0f;
   put(t0, g2, c, h); put(t1, c1, c, h);
@@ -197,13 +111,13 @@ __device__ __forceinline__ void critic_step(const float4 (*wimg)[64], int q0, co
   get(t0, ta_, c, h); get(t1, tb_, c, h);
   wave_lds_sync();
 #pragma unroll
-  for (int s = 0; s < 16; s++) { acc.gW2 = DDPG_MFMA(ta_[s], tb_[s], acc.gW2); acc.gW2a = DDPG_MFMA(ta_[s], at[s], acc.gW2a); acc.gb2 += ta_[s]; }
+  for (int s = 0; s < 16; s++) { acc.gW2 = TILE_MFMA(ta_[s], tb_[s], acc.gW2); acc.gW2a = TILE_MFMA(ta_[s], at[s], acc.gW2a); acc.gb2 += ta_[s]; }
   put(t0, g1, c, h);
   wave_lds_sync();
   get(t0, ta_, c, h);
   wave_lds_sync();
 #pragma unroll
-  for (int s = 0; s < 16; s++) acc.gW1 = DDPG_MFMA(ta_[s], xt[s], acc.gW1);
+  for (int s = 0; s < 16; s++) acc.gW1 = TILE_MFMA(ta_[s], xt[s], acc.gW1);
 }
 // this wavefront's row of a critic into LDS (tu_ddpg.hip's order)
 template <int D, int A> __device__ __forceinline__ void critic_row(CriticAcc& a, float* red, int lane, int c, int h) {
@@ -278,7 +192,7 @@ inline int blocks_for(int n) {
 }
 inline int policy_step_grid(int n) { return ((n + 31) / 32 + WAVES - 1) / WAVES; }   // the policy-step kernels: one tile per wavefront
 inline bool shape_ok(int D, int A) { return (D == 26 || D == 17) && (A == 6 || A == 7); }
-inline bool net_ok(const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3) { return W1 && b1 && W2 && b2 && W3 && b3; }
+inline bool net_ok(const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3) { return net_ok(Net{W1, b1, W2, b2, W3, b3}); }
 // a network as the C ABI passes it: a host array of the six device pointers {W1, b1, W2, b2, W3, b3}
 template <class P> inline bool net_ok(P p) { return p && net_ok(p[0], p[1], p[2], p[3], p[4], p[5]); }
 inline Net net_of(const float* const* p) { return Net{p[0], p[1], p[2], p[3], p[4], p[5]}; }

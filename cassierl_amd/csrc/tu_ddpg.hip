@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, c
       v16f mu = bias_tile(sbias[2], h);
       aop(wimg, CQ_TA_W3, lane, aw);
 #pragma unroll
-      for (int v = 0; v < 16; v++) mu = DDPG_MFMA(aw[v], a2[v], mu);
+      for (int v = 0; v < 16; v++) mu = TILE_MFMA(aw[v], a2[v], mu);
 #pragma unroll
       for (int v = 0; v < 4; v++) mt[v] = tanh_fast(mu[v]);   // rows a >= A: W3 and b3 padded with zeros -> tanh(0) = 0
     }
@@ -132,7 +132,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, c
     float aw[16], ta_[16], tb_[16];
     aop(wimg, CQ_Q_W2T, lane, aw);
 #pragma unroll
-    for (int v = 0; v < 16; v++) g1 = DDPG_MFMA(aw[v], g2[v], g1);
+    for (int v = 0; v < 16; v++) g1 = TILE_MFMA(aw[v], g2[v], g1);
 #pragma unroll
     for (int v = 0; v < 16; v++) g1[v] = c1[v] > 0.0f ? g1[v] : 0.0f;
     put(t0, g2, c, h); put(t1, c1, c, h);
@@ -140,13 +140,13 @@ __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, c
     get(t0, ta_, c, h); get(t1, tb_, c, h);
     wave_lds_sync();
 #pragma unroll
-    for (int s = 0; s < 16; s++) { gW2 = DDPG_MFMA(ta_[s], tb_[s], gW2); gW2a = DDPG_MFMA(ta_[s], at[s], gW2a); gb2 += ta_[s]; }
+    for (int s = 0; s < 16; s++) { gW2 = TILE_MFMA(ta_[s], tb_[s], gW2); gW2a = TILE_MFMA(ta_[s], at[s], gW2a); gb2 += ta_[s]; }
     put(t0, g1, c, h);
     wave_lds_sync();
     get(t0, ta_, c, h);
     wave_lds_sync();
 #pragma unroll
-    for (int s = 0; s < 16; s++) gW1 = DDPG_MFMA(ta_[s], xt[s], gW1);
+    for (int s = 0; s < 16; s++) gW1 = TILE_MFMA(ta_[s], xt[s], gW1);
   }
   // ---- this wavefront's row in LDS (the tiles are free once every wavefront has left the loop), then one row per workgroup
 #pragma unroll
@@ -231,7 +231,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
       v16f z3 = bias_tile(sbias[2], h);
       aop(wimg, AG_W3, lane, aw);
 #pragma unroll
-      for (int v = 0; v < 16; v++) z3 = DDPG_MFMA(aw[v], a2[v], z3);
+      for (int v = 0; v < 16; v++) z3 = TILE_MFMA(aw[v], a2[v], z3);
 #pragma unroll
       for (int v = 0; v < 4; v++) mu[v] = tanh_fast(z3[v]);
     }
@@ -246,7 +246,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
     for (int v = 0; v < 16; v++) da[v] = 0.0f;
     aop(wimg, AG_Q_DA, lane, aw);
 #pragma unroll
-    for (int v = 0; v < 16; v++) da = DDPG_MFMA(aw[v], c2[v] > 0.0f ? w3q[v] : 0.0f, da);
+    for (int v = 0; v < 16; v++) da = TILE_MFMA(aw[v], c2[v] > 0.0f ? w3q[v] : 0.0f, da);
     // cotangent of -Q on the output layer's pre-activation
     v16f wt;
 #pragma unroll
@@ -259,13 +259,13 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
     for (int v = 0; v < 16; v++) { g2[v] = 0.0f; g1[v] = 0.0f; }
     {
       const float4 w = wimg[AG_W3T][lane];
-      g2 = DDPG_MFMA(w.x, wt[0], g2); g2 = DDPG_MFMA(w.y, wt[1], g2); g2 = DDPG_MFMA(w.z, wt[2], g2); g2 = DDPG_MFMA(w.w, wt[3], g2);
+      g2 = TILE_MFMA(w.x, wt[0], g2); g2 = TILE_MFMA(w.y, wt[1], g2); g2 = TILE_MFMA(w.z, wt[2], g2); g2 = TILE_MFMA(w.w, wt[3], g2);
     }
 #pragma unroll
     for (int v = 0; v < 16; v++) g2[v] = a2[v] > 0.0f ? g2[v] : 0.0f;
     aop(wimg, AG_W2T, lane, aw);
 #pragma unroll
-    for (int v = 0; v < 16; v++) g1 = DDPG_MFMA(aw[v], g2[v], g1);
+    for (int v = 0; v < 16; v++) g1 = TILE_MFMA(aw[v], g2[v], g1);
 #pragma unroll
     for (int v = 0; v < 16; v++) g1[v] = a1[v] > 0.0f ? g1[v] : 0.0f;
     float ta_[16], tb_[16];
@@ -274,19 +274,19 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
     get(t0, ta_, c, h); get(t1, tb_, c, h);
     wave_lds_sync();
 #pragma unroll
-    for (int s = 0; s < 16; s++) { gW2 = DDPG_MFMA(ta_[s], tb_[s], gW2); gb2 += ta_[s]; }
+    for (int s = 0; s < 16; s++) { gW2 = TILE_MFMA(ta_[s], tb_[s], gW2); gb2 += ta_[s]; }
     put(t0, g1, c, h);
     wave_lds_sync();
     get(t0, ta_, c, h);
     wave_lds_sync();
 #pragma unroll
-    for (int s = 0; s < 16; s++) gW1 = DDPG_MFMA(ta_[s], xt[s], gW1);
+    for (int s = 0; s < 16; s++) gW1 = TILE_MFMA(ta_[s], xt[s], gW1);
     put(t0, wt, c, h); put(t1, a2, c, h);
     wave_lds_sync();
     get(t0, ta_, c, h); get(t1, tb_, c, h);
     wave_lds_sync();
 #pragma unroll
-    for (int s = 0; s < 16; s++) { gW3 = DDPG_MFMA(ta_[s], tb_[s], gW3); gb3 += ta_[s]; }
+    for (int s = 0; s < 16; s++) { gW3 = TILE_MFMA(ta_[s], tb_[s], gW3); gb3 += ta_[s]; }
   }
 #pragma unroll
   for (int m = 16; m >= 1; m >>= 1) sq += __shfl_xor(sq, m, 64);
@@ -353,15 +353,15 @@ __global__ void __launch_bounds__(64 * WAVES, 2) policy_step_kernel(const double
   }
   v16f h1 = bias_tile(sbias[0], h);
 #pragma unroll
-  for (int s = 0; s < KS1; s++) h1 = DDPG_MFMA(aW1[s], xb[s], h1);
+  for (int s = 0; s < KS1; s++) h1 = TILE_MFMA(aW1[s], xb[s], h1);
   relu16(h1);
   v16f h2 = bias_tile(sbias[1], h);
 #pragma unroll
-  for (int v = 0; v < 16; v++) h2 = DDPG_MFMA(aW2[v], h1[v], h2);
+  for (int v = 0; v < 16; v++) h2 = TILE_MFMA(aW2[v], h1[v], h2);
   relu16(h2);
   v16f z3 = bias_tile(sbias[2], h);
 #pragma unroll
-  for (int v = 0; v < 16; v++) z3 = DDPG_MFMA(aW3[v], h2[v], z3);
+  for (int v = 0; v < 16; v++) z3 = TILE_MFMA(aW3[v], h2[v], z3);
   const bool fresh = valid && path_t[smp] == 0;
 #pragma unroll
   for (int v = 0; v < 4; v++) {

@@ -19,6 +19,7 @@
 
 #include "../../include/cassie_trpo.h"
 #include "../../include/cassie_vec.h"
+#include "cassie_tiles.h"   // tanh_fast, wave_lds_sync
 
 namespace cassie_es {
 
@@ -30,14 +31,8 @@ constexpr int GRAD_BLOCK = 256;     // parameters per workgroup of the gradient 
 constexpr int GRAD_MAX_ROWS = 128;
 constexpr int GRAD_MIN_CHUNK = 64;  // directions per row before a second row is opened
 
-// tu_trpo.hip's tanh: 1 - 2 / (e^2x + 1) through the hardware exp2 / rcp, absolute error ~1e-7, exact at the saturated ends
-__device__ __forceinline__ float tanh_fast(float x) {
-  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
-}
-__device__ __forceinline__ void wave_lds_sync() {   // a wavefront's LDS accesses complete in order; this keeps the compiler from moving them
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using cassie_tiles::tanh_fast;       // 1 - 2 / (e^2x + 1) through the hardware exp2 / rcp, absolute error ~1e-7, exact at the saturated ends
+using cassie_tiles::wave_lds_sync;
 
 // The parameter row [W1 | b1 | W2 | b2 | W3 | b3] (mlp32_tiles.h's actor row) and its padded image in LDS.
 template <int D, int A> struct Shape {

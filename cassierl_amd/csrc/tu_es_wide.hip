@@ -21,6 +21,7 @@
 
 #include "../../include/cassie_trpo.h"
 #include "../../include/cassie_vec.h"
+#include "cassie_tiles.h"   // tanh_fast, wave_lds_sync
 
 namespace cassie_es_wide {
 
@@ -33,14 +34,8 @@ constexpr int NCH = H / CH;
 constexpr int UPL = H / 32;         // hidden units per lane
 constexpr int HP = H + 4;           // row length of W2 in the images: 4 (mod 64), so that the 16-byte reads of a 16-lane group cover the 64 banks
 
-// tu_trpo.hip's tanh: 1 - 2 / (e^2x + 1) through the hardware exp2 / rcp, absolute error ~1e-7, exact at the saturated ends
-__device__ __forceinline__ float tanh_fast(float x) {
-  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
-}
-__device__ __forceinline__ void wave_lds_sync() {   // a wavefront's LDS accesses complete in order; this keeps the compiler from moving them
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using cassie_tiles::tanh_fast;       // 1 - 2 / (e^2x + 1) through the hardware exp2 / rcp, absolute error ~1e-7, exact at the saturated ends
+using cassie_tiles::wave_lds_sync;
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 // The parameter row [W1 | b1 | W2 | b2 | W3 | b3], its chunks and the padded images in LDS.

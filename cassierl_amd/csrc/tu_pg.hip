@@ -18,6 +18,9 @@
 //     the 32-row quarter q of gW1, gW2 and the 32-column quarter q of gW3 from all four tiles (96 accumulator registers).  One row of
 //     partial sums per WORKGROUP; the caller adds the rows;
 //   * the 6- or 7-row output layer is padded to 32 rows, as in tu_trpo.hip (64 of the 372 MFMAs of a forward tile).
+// Where the pieces live: the layout primitives in cassie_tiles.h; shapes, forward pass, wave_put / wave_get and vjp_blocks in cassie_pg_net.h; the VJP's
+// reverse pass of a group and the workgroup's row store in cassie_pg_vjp.inc / cassie_pg_vjp_row.inc (text shared with tu_ppo.hip's clip-gradient
+// kernel); the (obs_dim, act_dim) dispatch and the argument check (launch_shape, net_ok16) in cassie_tiles.h.
 // Every sum runs in a fixed order (k-ordered MFMA chains, tiles in a fixed order per workgroup, a fixed grid for a given n): a run
 // repeats bit for bit.
 #include <hip/hip_runtime.h>
@@ -25,7 +28,7 @@
 
 #include "../../include/cassie_trpo.h"
 #include "../../include/cassie_vec.h"
-#include "cassie_pg_net.h"   // H, WAVES, Shape, Net, tanh_fast, bias_tile, gemm_block, forward_hidden (shared with tu_pg_trpo.hip)
+#include "cassie_pg_net.h"   // H, WAVES, Shape, gemm_block, forward_hidden, wave_put, wave_get (shared with tu_pg_trpo.hip, tu_ppo.hip)
 
 namespace cassie_pg {
 
@@ -80,20 +83,6 @@ __global__ void __launch_bounds__(64 * WAVES, 2) pg_policy_step_kernel(const dou
 }
 
 // ---------------------------------------------------------------------------------------------------------------- VJP
-__device__ __forceinline__ void wave_put(float* __restrict__ t, const v16f (&x)[NB], int c, int h) {   // accumulator layout -> [row][sample]
-#pragma unroll
-  for (int b = 0; b < NB; b++)
-#pragma unroll
-    for (int v = 0; v < 16; v++) t[(32 * b + (v & 3) + 8 * (v >> 2) + 4 * h) * TP + c] = x[b][v];
-}
-__device__ __forceinline__ void wave_get(const float* __restrict__ t, float (&y)[16], int c, int h) {   // lane (c, h): row c, samples 16 h .. 16 h + 15
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const float4 b = *reinterpret_cast<const float4*>(&t[c * TP + 16 * h + 4 * q]);
-    y[4 * q] = b.x; y[4 * q + 1] = b.y; y[4 * q + 2] = b.z; y[4 * q + 3] = b.w;
-  }
-}
-
 // partial [gridDim.x][NP]: J' w of this workgroup's tiles, [gW1 | gb1 | gW2 | gb2 | gW3 | gb3].  Wavefront q writes rows 32 q .. 32 q + 31
 // of gW1 / gb1 / gW2 / gb2 and columns 32 q .. 32 q + 31 of gW3; wavefront 0 writes gb3.
 template <int D, int A>
@@ -127,101 +116,16 @@ __global__ void __launch_bounds__(64 * WAVES, 1) pg_vjp_kernel(const float* __re
     float wt[4];
 #pragma unroll
     for (int v = 0; v < 4; v++) wt[v] = (valid && v + 4 * h < A) ? wext[(size_t)smp * A + v + 4 * h] : 0.0f;
-    // G2 = (W3' w) o (1 - H2^2): k-step v sums over the cotangent row a = v + 4 h
-#pragma unroll
-    for (int ob = 0; ob < NB; ob++) {
-      v16f y = zero16();
-#pragma unroll
-      for (int v = 0; v < 4; v++) {
-        const int a = v + 4 * h;
-        y = PG_MFMA(a < A ? th.W3[a * H + 32 * ob + c] : 0.0f, wt[v], y);
-      }
-#pragma unroll
-      for (int v = 0; v < 16; v++) y[v] *= 1.0f - h2[ob][v] * h2[ob][v];
-      g2[ob] = y;
-    }
-    // Three exchanges through the two LDS slots, so that no more than two 128 x 32 activations of the tile are live in registers:
-    // ---- 1. H1 (slot 0, kept to the third exchange) and H2 (slot 1): gW3[a][32 q + j] += sum_s w[s][a] H2[32 q + j][s]
-    wave_put(stage[0][wave], h1, c, h);
-    wave_put(stage[1][wave], h2, c, h);
-    __syncthreads();
-#pragma unroll 1
-    for (int u = 0; u < WAVES; u++) {
-      float ta[16], wa[16];
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const int sm = gs0 + 32 * u + 16 * h + e;   // the sample of k-step e
-        wa[e] = (c < A && sm < n) ? wext[(size_t)sm * A + c] : 0.0f;
-      }
-      wave_get(stage[1][u] + 32 * wave * TP, ta, c, h);
-#pragma unroll
-      for (int s = 0; s < 16; s++) { gW3 = PG_MFMA(wa[s], ta[s], gW3); gb3 += wa[s]; }
-    }
-    // ---- 2. G2 (slot 1): gW2[32 q + i][32 kb + j] += sum_s G2[32 q + i][s] H1[32 kb + j][s]
-    __syncthreads();
-    wave_put(stage[1][wave], g2, c, h);
-    __syncthreads();
-    // G1 = (W2' G2) o (1 - H1^2) of this wavefront's tile (H1 from its slot-0 image): k-step v of block (ob, kb) reads W2[32 kb + r(v, h)][32 ob + c]
-    const float* myh1 = stage[0][wave];
-#pragma unroll
-    for (int ob = 0; ob < NB; ob++) {
-      v16f y = zero16();
-#pragma unroll
-      for (int kb = 0; kb < NB; kb++)
-#pragma unroll
-        for (int v = 0; v < 16; v++) y = PG_MFMA(th.W2[(size_t)(32 * kb + (v & 3) + 8 * (v >> 2) + 4 * h) * H + 32 * ob + c], g2[kb][v], y);
-#pragma unroll
-      for (int v = 0; v < 16; v++) {
-        const float x = myh1[(32 * ob + (v & 3) + 8 * (v >> 2) + 4 * h) * TP + c];
-        y[v] *= 1.0f - x * x;
-      }
-      g1[ob] = y;
-    }
-#pragma unroll 1
-    for (int u = 0; u < WAVES; u++) {
-      float ta[16], tb[16];
-      wave_get(stage[1][u] + 32 * wave * TP, ta, c, h);
-#pragma unroll
-      for (int s = 0; s < 16; s++) gb2 += ta[s];
-#pragma unroll
-      for (int kb = 0; kb < NB; kb++) {
-        wave_get(stage[0][u] + 32 * kb * TP, tb, c, h);
-#pragma unroll
-        for (int s = 0; s < 16; s++) gW2[kb] = PG_MFMA(ta[s], tb[s], gW2[kb]);
-      }
-    }
-    // ---- 3. G1 (slot 0): gW1[32 q + i][k] += sum_s G1[32 q + i][s] [obs | 1][s][k]   (column D: gb1)
-    __syncthreads();
-    wave_put(stage[0][wave], g1, c, h);
-    __syncthreads();
-#pragma unroll 1
-    for (int u = 0; u < WAVES; u++) {
-      float ta[16], xt[16];
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const int sm = gs0 + 32 * u + 16 * h + e;
-        xt[e] = c < D ? (sm < n ? obs[(size_t)sm * D + c] : 0.0f) : (c == D ? 1.0f : 0.0f);
-      }
-      wave_get(stage[0][u] + 32 * wave * TP, ta, c, h);
-#pragma unroll
-      for (int s = 0; s < 16; s++) gW1 = PG_MFMA(ta[s], xt[s], gW1);
-    }
+    // the reverse pass of the group reads the cotangent and the observations of the OTHER wavefronts' tiles, transposed, from memory
+#define PG_VJP_COT_ROW(u, wa) \
+  _Pragma("unroll") for (int e = 0; e < 16; e++) { const int sm = gs0 + 32 * (u) + 16 * h + e; (wa)[e] = (c < A && sm < n) ? wext[(size_t)sm * A + c] : 0.0f; }   // sm: the sample of k-step e
+#define PG_VJP_OBS_T(u, e, x) { const int sm = gs0 + 32 * (u) + 16 * h + (e); (x) = c < D ? (sm < n ? obs[(size_t)sm * D + c] : 0.0f) : (c == D ? 1.0f : 0.0f); }
+#include "cassie_pg_vjp.inc"
+#undef PG_VJP_COT_ROW
+#undef PG_VJP_OBS_T
   }
-  // ---- this workgroup's row: gW[r(v, h)][c] in register v
   float* out = partial + (size_t)blockIdx.x * S::NP;
-  const int q = wave;
-#pragma unroll
-  for (int v = 0; v < 16; v++) {
-    const int r = (v & 3) + 8 * (v >> 2) + 4 * h;
-#pragma unroll
-    for (int kb = 0; kb < NB; kb++) out[S::O_W2 + (32 * q + r) * H + 32 * kb + c] = gW2[kb][v];
-    if (c < D) out[S::O_W1 + (32 * q + r) * D + c] = gW1[v];
-    if (c == D) out[S::O_B1 + 32 * q + r] = gW1[v];
-    if (r < A) out[S::O_W3 + r * H + 32 * q + c] = gW3[v];
-  }
-  gb2 += __shfl_xor(gb2, 32, 64); gb3 += __shfl_xor(gb3, 32, 64);
-  if (h == 0) out[S::O_B2 + 32 * q + c] = gb2;
-  if (q == 0 && h == 0 && c < A) out[S::O_B3 + c] = gb3;
+#include "cassie_pg_vjp_row.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------------- Adam
@@ -239,10 +143,6 @@ __global__ void __launch_bounds__(256) pg_adam_kernel(int n, const float* __rest
 }
 
 inline int step_blocks(int n) { return ((n + 31) / 32 + WAVES - 1) / WAVES; }
-inline int vjp_blocks(int n) {
-  const int groups = ((n + 31) / 32 + WAVES - 1) / WAVES;
-  return groups < 1 ? 1 : (groups > MAX_VJP_BLOCKS ? MAX_VJP_BLOCKS : groups);
-}
 }  // namespace cassie_pg
 
 extern "C" {
@@ -258,40 +158,30 @@ int CassiePgPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, c
                        const double* low_dev, const double* high_dev, float* obs32_dev, float* mean_dev, float* act_dev,
                        double* env_actions_dev, void* stream) {
   using namespace cassie_pg;
-  if (!obs_dev || n <= 0 || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !log_std || !noise_dev || !low_dev || !high_dev || !obs32_dev || !mean_dev ||
-      !act_dev || !env_actions_dev)
-    return CASSIE_EINVAL;
-  if (!aligned16(b1) || !aligned16(W2) || !aligned16(b2) || !aligned16(W3)) return CASSIE_EINVAL;   // read as float4
   const Net th{W1, b1, W2, b2, W3, b3};
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(step_blocks(n)), block(64 * WAVES);
-  if (obs_dim == 26 && act_dim == 6) hipLaunchKernelGGL((pg_policy_step_kernel<26, 6>), grid, block, 0, s, obs_dev, n, th, log_std, noise_dev, low_dev, high_dev, obs32_dev, mean_dev, act_dev, env_actions_dev);
-  else if (obs_dim == 26 && act_dim == 7) hipLaunchKernelGGL((pg_policy_step_kernel<26, 7>), grid, block, 0, s, obs_dev, n, th, log_std, noise_dev, low_dev, high_dev, obs32_dev, mean_dev, act_dev, env_actions_dev);
-  else return CASSIE_EINVAL;
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  if (!obs_dev || n <= 0 || !net_ok16(th) || !log_std || !noise_dev || !low_dev || !high_dev || !obs32_dev || !mean_dev || !act_dev || !env_actions_dev)
+    return CASSIE_EINVAL;
+  return launch_shape<true>(obs_dim, act_dim, [&](auto d, auto a) {
+    hipLaunchKernelGGL((pg_policy_step_kernel<d(), a()>), dim3(step_blocks(n)), dim3(64 * WAVES), 0, (hipStream_t)stream, obs_dev, n, th, log_std, noise_dev, low_dev, high_dev,
+                       obs32_dev, mean_dev, act_dev, env_actions_dev);
+  });
 }
 
 int CassiePgVjp(const float* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2,
                 const float* W3, const float* b3, const float* w_dev, float* partial_dev, void* stream) {
   using namespace cassie_pg;
-  if (!obs_dev || n <= 0 || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !w_dev || !partial_dev) return CASSIE_EINVAL;
-  if (!aligned16(b1) || !aligned16(W2) || !aligned16(b2) || !aligned16(W3)) return CASSIE_EINVAL;
   const Net th{W1, b1, W2, b2, W3, b3};
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(vjp_blocks(n)), block(64 * WAVES);
-  if (obs_dim == 26 && act_dim == 6) hipLaunchKernelGGL((pg_vjp_kernel<26, 6>), grid, block, 0, s, obs_dev, n, th, w_dev, partial_dev);
-  else if (obs_dim == 26 && act_dim == 7) hipLaunchKernelGGL((pg_vjp_kernel<26, 7>), grid, block, 0, s, obs_dev, n, th, w_dev, partial_dev);
-  else if (obs_dim == 17 && act_dim == 6) hipLaunchKernelGGL((pg_vjp_kernel<17, 6>), grid, block, 0, s, obs_dev, n, th, w_dev, partial_dev);
-  else if (obs_dim == 17 && act_dim == 7) hipLaunchKernelGGL((pg_vjp_kernel<17, 7>), grid, block, 0, s, obs_dev, n, th, w_dev, partial_dev);
-  else return CASSIE_EINVAL;
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  if (!obs_dev || n <= 0 || !net_ok16(th) || !w_dev || !partial_dev) return CASSIE_EINVAL;
+  return launch_shape(obs_dim, act_dim, [&](auto d, auto a) {
+    hipLaunchKernelGGL((pg_vjp_kernel<d(), a()>), dim3(vjp_blocks(n)), dim3(64 * WAVES), 0, (hipStream_t)stream, obs_dev, n, th, w_dev, partial_dev);
+  });
 }
 
 int CassiePgAdam(int n, const float* g, float* m, float* v, float* theta, int t, float lr, float beta1, float beta2, float eps, void* stream) {
   if (n <= 0 || !g || !m || !v || !theta || t < 1) return CASSIE_EINVAL;
   const double a = (double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t));
   hipLaunchKernelGGL(cassie_pg::pg_adam_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, g, m, v, theta, (float)a, beta1, beta2, eps);
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  return cassie_tiles::launched();
 }
 
 }  // extern "C"

@@ -9,12 +9,15 @@
 // The product runs in two launches: a forward-mode kernel writes the per-sample cotangent w = scale * prec * (J v) [n][act_dim], and
 // CassiePgVjp (tu_pg.hip, unchanged) takes it back to the parameters.  Fusing the two would add the tangents dH1 / dH2 to the VJP's
 // registers (256 VGPRs + ~230 AGPRs already) for a saving of one 12.6 MB write and read at 524 288 samples.
+// Where the pieces live: the layout primitives, the argument check (net_ok16) and the (obs_dim, act_dim) dispatch (launch_shape) in cassie_tiles.h; the
+// forward pass in cassie_pg_net.h; the CG step's kernel (cg_update_kernel<CG_PER>, one body for both widths) in cassie_onpolicy.h.
 // Every sum runs in a fixed order: a run repeats bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/cassie_trpo.h"
 #include "../../include/cassie_vec.h"
+#include "cassie_onpolicy.h"   // cg_update_kernel
 #include "cassie_pg_net.h"
 
 namespace cassie_pg {
@@ -42,8 +45,8 @@ __global__ void __launch_bounds__(64 * WAVES, 1) pg_jvp_kernel(const float* __re
     for (int s = 0; s < KS1; s++) {
       const int k = 2 * s + h;
       const float a = k < D ? th.W1[(32 * ob + c) * D + k] : 0.0f, da = k < D ? dir.W1[(32 * ob + c) * D + k] : 0.0f;
-      y = PG_MFMA(a, xb[s], y);
-      dy = PG_MFMA(da, xb[s], dy);
+      y = TILE_MFMA(a, xb[s], y);
+      dy = TILE_MFMA(da, xb[s], dy);
     }
 #pragma unroll
     for (int v = 0; v < 16; v++) { y[v] = tanh_fast(y[v]); dy[v] *= 1.0f - y[v] * y[v]; }
@@ -136,65 +139,11 @@ __global__ void __launch_bounds__(64 * WAVES, 2) pg_surrogate_kernel(const float
 }
 
 // ---------------------------------------------------------------------------------------------------------------- CG vector step
-// tu_trpo.hip's cg_update_kernel for a parameter vector of up to CG_MAX entries (the 128-128 network: 20 878 at 26 -> 7), one workgroup of
-// 1024 threads, entry i = threadIdx.x + 1024 k in register k.  Dot products: per thread in k order, then the fixed-order block sum.
+// cassie_onpolicy.h's cg_update_kernel for a parameter vector of up to CG_MAX entries (the 128-128 network: 20 878 at 26 -> 7): CG_PER entries per thread.
 constexpr int CG_PER = 21;
 constexpr int CG_MAX = 1024 * CG_PER;
 
-__device__ __forceinline__ float block_sum_1024(float v, float* red) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float t = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 16; i++) t += red[i];   // every thread adds the 16 wavefront sums in the same order
-  return t;
-}
-
-__global__ void __launch_bounds__(1024) pg_cg_update_kernel(int n, int ls_off, int n_ls, const float* __restrict__ Apm, const float* __restrict__ hls, float reg,
-                                                           float tol, float* __restrict__ x, float* __restrict__ r, float* __restrict__ p, float* __restrict__ scal) {
-  __shared__ float red[16];
-  float pv[CG_PER], ap[CG_PER], rv[CG_PER];
-  float s = 0.0f;
-#pragma unroll
-  for (int k = 0; k < CG_PER; k++) {
-    const int i = threadIdx.x + 1024 * k;
-    pv[k] = 0.0f; ap[k] = 0.0f; rv[k] = 0.0f;
-    if (i < n) {
-      pv[k] = p[i]; rv[k] = r[i];
-      const bool ls = i >= ls_off && i < ls_off + n_ls;
-      const float f = ls ? hls[i - ls_off] * pv[k] : Apm[i < ls_off ? i : i - n_ls];
-      ap[k] = f + reg * pv[k];
-      s += pv[k] * ap[k];
-    }
-  }
-  const float pAp = block_sum_1024(s, red);
-  const float rr = scal[0];
-  const bool running = scal[1] != 0.0f;
-  const float alpha = running ? rr / pAp : 0.0f;
-  s = 0.0f;
-#pragma unroll
-  for (int k = 0; k < CG_PER; k++) {
-    const int i = threadIdx.x + 1024 * k;
-    if (i < n) { x[i] += alpha * pv[k]; rv[k] -= alpha * ap[k]; r[i] = rv[k]; s += rv[k] * rv[k]; }
-  }
-  const float rr_new = block_sum_1024(s, red);
-  const bool go_on = running && rr_new >= tol;
-  const float beta = go_on ? rr_new / rr : 0.0f;
-#pragma unroll
-  for (int k = 0; k < CG_PER; k++) {
-    const int i = threadIdx.x + 1024 * k;
-    if (i < n) p[i] = rv[k] + beta * pv[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) { scal[0] = rr_new; scal[1] = go_on ? 1.0f : 0.0f; }
-}
-
 inline int tile_blocks(int n) { return ((n + 31) / 32 + WAVES - 1) / WAVES; }
-inline bool net_ok(const Net& t) { return t.W1 && t.b1 && t.W2 && t.b2 && t.W3 && t.b3 && aligned16(t.b1) && aligned16(t.W2) && aligned16(t.b2) && aligned16(t.W3); }
 
 }  // namespace cassie_pg
 
@@ -205,15 +154,11 @@ int CassiePgFvp(const float* obs_dev, int n, int obs_dim, int act_dim, const flo
                 const float* db3, const float* prec, float scale, float* work_dev, float* partial_dev, void* stream) {
   using namespace cassie_pg;
   const Net th{W1, b1, W2, b2, W3, b3}, dir{dW1, db1, dW2, db2, dW3, db3};
-  if (!obs_dev || n <= 0 || !net_ok(th) || !net_ok(dir) || !prec || !work_dev || !partial_dev) return CASSIE_EINVAL;
-  if (CassiePgParamCount(obs_dim, act_dim) == 0) return CASSIE_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(tile_blocks(n)), block(64 * WAVES);
-  if (obs_dim == 26 && act_dim == 6) hipLaunchKernelGGL((pg_jvp_kernel<26, 6>), grid, block, 0, s, obs_dev, n, th, dir, prec, scale, work_dev);
-  else if (obs_dim == 26 && act_dim == 7) hipLaunchKernelGGL((pg_jvp_kernel<26, 7>), grid, block, 0, s, obs_dev, n, th, dir, prec, scale, work_dev);
-  else if (obs_dim == 17 && act_dim == 6) hipLaunchKernelGGL((pg_jvp_kernel<17, 6>), grid, block, 0, s, obs_dev, n, th, dir, prec, scale, work_dev);
-  else hipLaunchKernelGGL((pg_jvp_kernel<17, 7>), grid, block, 0, s, obs_dev, n, th, dir, prec, scale, work_dev);
-  if (hipGetLastError() != hipSuccess) return CASSIE_EHIP;
+  if (!obs_dev || n <= 0 || !net_ok16(th) || !net_ok16(dir) || !prec || !work_dev || !partial_dev) return CASSIE_EINVAL;
+  const int rc = launch_shape(obs_dim, act_dim, [&](auto d, auto a) {
+    hipLaunchKernelGGL((pg_jvp_kernel<d(), a()>), dim3(tile_blocks(n)), dim3(64 * WAVES), 0, (hipStream_t)stream, obs_dev, n, th, dir, prec, scale, work_dev);
+  });
+  if (rc != CASSIE_OK) return rc;
   return CassiePgVjp(obs_dev, n, obs_dim, act_dim, W1, b1, W2, b2, W3, b3, work_dev, partial_dev, stream);
 }
 
@@ -224,23 +169,19 @@ int CassiePgSurrogate(const float* obs_dev, int n, int obs_dim, int act_dim, con
                       const float* adv_dev, const float* old_mean_dev, double* partial_dev, void* stream) {
   using namespace cassie_pg;
   const Net th{W1, b1, W2, b2, W3, b3};
-  if (!obs_dev || n <= 0 || !net_ok(th) || !log_std_new || !log_std_old || !act_dev || !adv_dev || !old_mean_dev || !partial_dev) return CASSIE_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(tile_blocks(n)), block(64 * WAVES);
-  if (obs_dim == 26 && act_dim == 6) hipLaunchKernelGGL((pg_surrogate_kernel<26, 6>), grid, block, 0, s, obs_dev, n, th, log_std_new, log_std_old, act_dev, adv_dev, old_mean_dev, partial_dev);
-  else if (obs_dim == 26 && act_dim == 7) hipLaunchKernelGGL((pg_surrogate_kernel<26, 7>), grid, block, 0, s, obs_dev, n, th, log_std_new, log_std_old, act_dev, adv_dev, old_mean_dev, partial_dev);
-  else if (obs_dim == 17 && act_dim == 6) hipLaunchKernelGGL((pg_surrogate_kernel<17, 6>), grid, block, 0, s, obs_dev, n, th, log_std_new, log_std_old, act_dev, adv_dev, old_mean_dev, partial_dev);
-  else if (obs_dim == 17 && act_dim == 7) hipLaunchKernelGGL((pg_surrogate_kernel<17, 7>), grid, block, 0, s, obs_dev, n, th, log_std_new, log_std_old, act_dev, adv_dev, old_mean_dev, partial_dev);
-  else return CASSIE_EINVAL;
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  if (!obs_dev || n <= 0 || !net_ok16(th) || !log_std_new || !log_std_old || !act_dev || !adv_dev || !old_mean_dev || !partial_dev) return CASSIE_EINVAL;
+  return launch_shape(obs_dim, act_dim, [&](auto d, auto a) {
+    hipLaunchKernelGGL((pg_surrogate_kernel<d(), a()>), dim3(tile_blocks(n)), dim3(64 * WAVES), 0, (hipStream_t)stream, obs_dev, n, th, log_std_new, log_std_old, act_dev,
+                       adv_dev, old_mean_dev, partial_dev);
+  });
 }
 
 int CassiePgCgUpdate(int n, int ls_off, int n_ls, const float* Ap_mean_dev, const float* hls_dev, float reg, float tol, float* x_dev, float* r_dev, float* p_dev,
                      float* scal_dev, void* stream) {
   if (n <= 0 || n > cassie_pg::CG_MAX || ls_off < 0 || n_ls < 0 || ls_off + n_ls > n || !Ap_mean_dev || !hls_dev || !x_dev || !r_dev || !p_dev || !scal_dev)
     return CASSIE_EINVAL;
-  hipLaunchKernelGGL(cassie_pg::pg_cg_update_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, ls_off, n_ls, Ap_mean_dev, hls_dev, reg, tol, x_dev, r_dev, p_dev, scal_dev);
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  hipLaunchKernelGGL(cassie_onpolicy::cg_update_kernel<cassie_pg::CG_PER>, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, ls_off, n_ls, Ap_mean_dev, hls_dev, reg, tol, x_dev, r_dev, p_dev, scal_dev);
+  return cassie_tiles::launched();
 }
 
 }  // extern "C"

@@ -59,7 +59,7 @@ __device__ __forceinline__ void actor_sample(const float4 (*wimg)[64], int qW1, 
   v16f z3 = bias_tile(sb3, h);
   aop(wimg, qW3, lane, aw);
 #pragma unroll
-  for (int v = 0; v < 16; v++) z3 = DDPG_MFMA(aw[v], a2[v], z3);
+  for (int v = 0; v < 16; v++) z3 = TILE_MFMA(aw[v], a2[v], z3);
   float lp = 0.0f;
 #pragma unroll
   for (int v = 0; v < 4; v++) {
@@ -255,10 +255,10 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
       qmin = first ? qa : qb;
       aop(wimg, AG_Q1 + AQ_DA, lane, aw);
 #pragma unroll
-      for (int v = 0; v < 16; v++) da = DDPG_MFMA(aw[v], (first && h2a[v] > 0.0f) ? wa[v] : 0.0f, da);
+      for (int v = 0; v < 16; v++) da = TILE_MFMA(aw[v], (first && h2a[v] > 0.0f) ? wa[v] : 0.0f, da);
       aop(wimg, AG_Q2 + AQ_DA, lane, aw);
 #pragma unroll
-      for (int v = 0; v < 16; v++) da = DDPG_MFMA(aw[v], (!first && h2b[v] > 0.0f) ? wb[v] : 0.0f, da);
+      for (int v = 0; v < 16; v++) da = TILE_MFMA(aw[v], (!first && h2b[v] > 0.0f) ? wb[v] : 0.0f, da);
     }
     if (h == 0 && valid) { slp += logpi; sq += qmin; }
     // cotangents of alpha log pi - min Q on the output layer: d/du = 2 alpha a~ - dQ/da (1 - a~^2) on the mean row, that times
@@ -279,14 +279,14 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
     for (int v = 0; v < 16; v++) { g2[v] = 0.0f; g1[v] = 0.0f; }
     {
       const float4 w = wimg[AG_W3T][lane], x = wimg[AG_W3T + 1][lane];
-      g2 = DDPG_MFMA(w.x, wt[0], g2); g2 = DDPG_MFMA(w.y, wt[1], g2); g2 = DDPG_MFMA(w.z, wt[2], g2); g2 = DDPG_MFMA(w.w, wt[3], g2);
-      g2 = DDPG_MFMA(x.x, wt[4], g2); g2 = DDPG_MFMA(x.y, wt[5], g2); g2 = DDPG_MFMA(x.z, wt[6], g2); g2 = DDPG_MFMA(x.w, wt[7], g2);
+      g2 = TILE_MFMA(w.x, wt[0], g2); g2 = TILE_MFMA(w.y, wt[1], g2); g2 = TILE_MFMA(w.z, wt[2], g2); g2 = TILE_MFMA(w.w, wt[3], g2);
+      g2 = TILE_MFMA(x.x, wt[4], g2); g2 = TILE_MFMA(x.y, wt[5], g2); g2 = TILE_MFMA(x.z, wt[6], g2); g2 = TILE_MFMA(x.w, wt[7], g2);
     }
 #pragma unroll
     for (int v = 0; v < 16; v++) g2[v] = a2[v] > 0.0f ? g2[v] : 0.0f;
     aop(wimg, AG_W2T, lane, aw);
 #pragma unroll
-    for (int v = 0; v < 16; v++) g1 = DDPG_MFMA(aw[v], g2[v], g1);
+    for (int v = 0; v < 16; v++) g1 = TILE_MFMA(aw[v], g2[v], g1);
 #pragma unroll
     for (int v = 0; v < 16; v++) g1[v] = a1[v] > 0.0f ? g1[v] : 0.0f;
     float ta_[16], tb_[16];
@@ -295,19 +295,19 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
     get(t0, ta_, c, h); get(t1, tb_, c, h);
     wave_lds_sync();
 #pragma unroll
-    for (int s = 0; s < 16; s++) { gW2 = DDPG_MFMA(ta_[s], tb_[s], gW2); gb2 += ta_[s]; }
+    for (int s = 0; s < 16; s++) { gW2 = TILE_MFMA(ta_[s], tb_[s], gW2); gb2 += ta_[s]; }
     put(t0, g1, c, h);
     wave_lds_sync();
     get(t0, ta_, c, h);
     wave_lds_sync();
 #pragma unroll
-    for (int s = 0; s < 16; s++) gW1 = DDPG_MFMA(ta_[s], xt[s], gW1);
+    for (int s = 0; s < 16; s++) gW1 = TILE_MFMA(ta_[s], xt[s], gW1);
     put(t0, wt, c, h); put(t1, a2, c, h);
     wave_lds_sync();
     get(t0, ta_, c, h); get(t1, tb_, c, h);
     wave_lds_sync();
 #pragma unroll
-    for (int s = 0; s < 16; s++) { gW3 = DDPG_MFMA(ta_[s], tb_[s], gW3); gb3 += ta_[s]; }
+    for (int s = 0; s < 16; s++) { gW3 = TILE_MFMA(ta_[s], tb_[s], gW3); gb3 += ta_[s]; }
   }
 #pragma unroll
   for (int m = 16; m >= 1; m >>= 1) { slp += __shfl_xor(slp, m, 64); sq += __shfl_xor(sq, m, 64); }
@@ -413,15 +413,15 @@ __global__ void __launch_bounds__(64 * WAVES, 2) policy_step_kernel(const double
   }
   v16f h1 = bias_tile(sbias[0], h);
 #pragma unroll
-  for (int s = 0; s < KS1; s++) h1 = DDPG_MFMA(aW1[s], xb[s], h1);
+  for (int s = 0; s < KS1; s++) h1 = TILE_MFMA(aW1[s], xb[s], h1);
   relu16(h1);
   v16f h2 = bias_tile(sbias[1], h);
 #pragma unroll
-  for (int v = 0; v < 16; v++) h2 = DDPG_MFMA(aW2[v], h1[v], h2);
+  for (int v = 0; v < 16; v++) h2 = TILE_MFMA(aW2[v], h1[v], h2);
   relu16(h2);
   v16f z3 = bias_tile(sbias[2], h);
 #pragma unroll
-  for (int v = 0; v < 16; v++) z3 = DDPG_MFMA(aW3[v], h2[v], z3);
+  for (int v = 0; v < 16; v++) z3 = TILE_MFMA(aW3[v], h2[v], z3);
 #pragma unroll
   for (int v = 0; v < 4; v++) {
     const int a = v + 4 * h;

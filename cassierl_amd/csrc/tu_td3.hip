@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, c
       v16f mu = bias_tile(sbias[2], h);
       aop(wimg, CQ_TA_W3, lane, aw);
 #pragma unroll
-      for (int v = 0; v < 16; v++) mu = DDPG_MFMA(aw[v], a2[v], mu);
+      for (int v = 0; v < 16; v++) mu = TILE_MFMA(aw[v], a2[v], mu);
 #pragma unroll
       for (int v = 0; v < 4; v++)   // rows a >= A: W3, b3 and the noise are zeros -> a' = 0, on zero columns of the merge layer's image
         an[v] = clip(tanh_fast(mu[v]) + clip(policy_noise * en[v], -noise_clip, noise_clip), -1.0f, 1.0f);
@@ -176,15 +176,15 @@ __global__ void __launch_bounds__(64 * WAVES, 2) policy_step_kernel(const double
   }
   v16f h1 = bias_tile(sbias[0], h);
 #pragma unroll
-  for (int s = 0; s < KS1; s++) h1 = DDPG_MFMA(aW1[s], xb[s], h1);
+  for (int s = 0; s < KS1; s++) h1 = TILE_MFMA(aW1[s], xb[s], h1);
   relu16(h1);
   v16f h2 = bias_tile(sbias[1], h);
 #pragma unroll
-  for (int v = 0; v < 16; v++) h2 = DDPG_MFMA(aW2[v], h1[v], h2);
+  for (int v = 0; v < 16; v++) h2 = TILE_MFMA(aW2[v], h1[v], h2);
   relu16(h2);
   v16f z3 = bias_tile(sbias[2], h);
 #pragma unroll
-  for (int v = 0; v < 16; v++) z3 = DDPG_MFMA(aW3[v], h2[v], z3);
+  for (int v = 0; v < 16; v++) z3 = TILE_MFMA(aW3[v], h2[v], z3);
 #pragma unroll
   for (int v = 0; v < 4; v++) {
     const int a = v + 4 * h;

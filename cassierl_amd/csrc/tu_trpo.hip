@@ -21,38 +21,22 @@
 //     all-reduces over ranks where it did before).
 // r04 history: a one-lane-per-sample FP32 vector version (weights through the scalar unit) was parity-green and SLOWER than torch
 // (0.80 ms against 0.67; weights in LDS 1.44 ms: the compiler hoists the weight reads and spills) -- replaced by this one.
+// Where the pieces live: the layout primitives, the A-operand images and the LDS transposes in cassie_tiles.h (shared with the ReLU networks
+// and the width-128 policy); the policy's row (Shape), the reverse pass of a tile with its gradient accumulation and row store, and the CG
+// vector step (cg_update_kernel; as torch operations ~15 launches per iteration, a third of what an iteration costs next to the 0.12 ms
+// product) in cassie_onpolicy.h (shared with tu_ppo.hip and tu_pg_trpo.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "../../include/cassie_trpo.h"
 #include "../../include/cassie_vec.h"
+#include "cassie_onpolicy.h"
 
 namespace cassie_trpo {
 
-constexpr int H = 32;         // hidden units (both layers)
-constexpr int TP = 36;        // floats per row of a transpose tile (16-byte aligned rows; ds_read_b128 of 16 lanes conflict-free)
-constexpr int WAVES = 4;      // wavefronts per workgroup: one per SIMD
-constexpr int MAX_BLOCKS = 512;   // two workgroups of four wavefronts per CU
-
-template <int D, int A> struct Shape {
-  static constexpr int NP = H * D + H + H * H + H + A * H + A;
-  static constexpr int O_W1 = 0, O_B1 = H * D, O_W2 = O_B1 + H, O_B2 = O_W2 + H * H, O_W3 = O_B2 + H, O_B3 = O_W3 + A * H;
-};
-
-struct Net { const float *W1, *b1, *W2, *b2, *W3, *b3; };
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-#define TRPO_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
-// tanh through the hardware exp2 / rcp: 1 - 2 / (e^2x + 1); absolute error ~1e-7 (the saturated ends are exact: e = inf or 0)
-__device__ __forceinline__ float tanh_fast(float x) {
-  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
-}
-__device__ __forceinline__ void wave_lds_sync() {   // a wavefront's LDS accesses complete in order; this keeps the compiler from moving them
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using namespace cassie_onpolicy;
+using namespace cassie_onpolicy::tanh32;   // H, TP, WAVES, MAX_BLOCKS, Shape, blocks_for, Grad, reverse_tile, store_row
 
 // FVP: w = S J dir (forward mode) per sample; otherwise w comes from memory.  Then J' w, accumulated per wavefront.
 // The A operands (weights in k-step order, see the header) are the same for every tile and every wavefront: the workgroup lays them
@@ -75,61 +59,23 @@ __global__ void __launch_bounds__(64 * WAVES, 2) trpo_kernel(const float* __rest
     sbias[0][tid] = th.b1[tid]; sbias[1][tid] = th.b2[tid];
     sbias[2][tid] = FVP ? dir.b1[tid] : 0.0f; sbias[3][tid] = FVP ? dir.b2[tid] : 0.0f; sbias[4][tid] = (FVP && tid < A) ? dir.b3[tid] : 0.0f;
   }
-  // ---- A operands, once per workgroup: element e of quad q = k-step 4 (q mod 4) + e of its matrix, for lane (i = c, h)
-  for (int q = wave; q < Q_N; q += WAVES) {
-    float v4[4];
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      const int st = 4 * (q & 3) + e;                       // k-step within the matrix
-      const int r = (st & 3) + 8 * (st >> 2) + 4 * h;       // accumulator-order row of that step (layers 2, 3 and the transposes)
-      const int k1 = 2 * st + h;                            // first layer: k = 2 s + h
-      float x = 0.0f;
-      if (q < Q_DW1) x = (st < KS1 && k1 < D) ? th.W1[c * D + k1] : 0.0f;
-      else if (q < Q_W2) x = (FVP && st < KS1 && k1 < D) ? dir.W1[c * D + k1] : 0.0f;
-      else if (q < Q_DW2) x = th.W2[c * H + r];
-      else if (q < Q_W3) x = FVP ? dir.W2[c * H + r] : 0.0f;
-      else if (q < Q_DW3) x = c < A ? th.W3[c * H + r] : 0.0f;
-      else if (q < Q_W2T) x = (FVP && c < A) ? dir.W3[c * H + r] : 0.0f;
-      else if (q < Q_W3T) x = th.W2[r * H + c];
-      else x = (e + 4 * h < A) ? th.W3[(e + 4 * h) * H + c] : 0.0f;   // W3': cotangent row a = v + 4 h
-      v4[e] = x;
-    }
-    wimg[q][lane] = make_float4(v4[0], v4[1], v4[2], v4[3]);
+  // ---- A operands, once per workgroup (the direction's images only where they are read)
+  if (FVP) {
+    const Grp img[] = {{K_FIRST, th.W1, Q_W1, 4}, {K_FIRST, dir.W1, Q_DW1, 4}, {K_HID, th.W2, Q_W2, 4}, {K_HID, dir.W2, Q_DW2, 4},
+                       {K_OUT, th.W3, Q_W3, 4}, {K_OUT, dir.W3, Q_DW3, 4}, {K_HIDT, th.W2, Q_W2T, 4}, {K_W3T, th.W3, Q_W3T, 1}};
+    fill_images<D, A>(wimg, img, wave, lane);
+  } else {
+    const Grp img[] = {{K_FIRST, th.W1, Q_W1, 4}, {K_HID, th.W2, Q_W2, 4}, {K_OUT, th.W3, Q_W3, 4}, {K_HIDT, th.W2, Q_W2T, 4}, {K_W3T, th.W3, Q_W3T, 1}};
+    fill_images<D, A>(wimg, img, wave, lane);
   }
   float pr[4];
 #pragma unroll
   for (int v = 0; v < 4; v++) { const int a = v + 4 * h; pr[v] = (FVP && a < A) ? prec[a] * scale : 0.0f; }
   __syncthreads();
-  auto aop = [&](int q0, float (&a)[16]) {   // the 16 k-steps of a product
-#pragma unroll
-    for (int q = 0; q < 4; q++) { const float4 w = wimg[q0 + q][lane]; a[4 * q] = w.x; a[4 * q + 1] = w.y; a[4 * q + 2] = w.z; a[4 * q + 3] = w.w; }
-  };
-  auto bias_tile = [&](int which) {   // C operand: bias[r(v, h)] in register v (rows 8 g + 4 h .. + 3 are one float4)
-    v16f z;
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-      const float4 b = *reinterpret_cast<const float4*>(&sbias[which][8 * g + 4 * h]);
-      z[4 * g] = b.x; z[4 * g + 1] = b.y; z[4 * g + 2] = b.z; z[4 * g + 3] = b.w;
-    }
-    return z;
-  };
   float* t0 = tile[wave][0];
   float* t1 = tile[wave][1];
-  auto put = [&](float* t, const v16f& x) {   // accumulator layout -> [row][sample] image
-#pragma unroll
-    for (int v = 0; v < 16; v++) t[((v & 3) + 8 * (v >> 2) + 4 * h) * TP + c] = x[v];
-  };
-  auto get = [&](const float* t, float (&y)[16]) {   // lane (i = c, h): row i, samples 16 h .. 16 h + 15
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const float4 b = *reinterpret_cast<const float4*>(&t[c * TP + 16 * h + 4 * q]);
-      y[4 * q] = b.x; y[4 * q + 1] = b.y; y[4 * q + 2] = b.z; y[4 * q + 3] = b.w;
-    }
-  };
-  v16f gW1, gW2, gW3;
-#pragma unroll
-  for (int v = 0; v < 16; v++) { gW1[v] = 0.0f; gW2[v] = 0.0f; gW3[v] = 0.0f; }
-  float gb2 = 0.0f, gb3 = 0.0f;
+  Grad g;
+  zero(g);
   const int ntiles = (n + 31) / 32;
   for (int tl = blockIdx.x * WAVES + wave; tl < ntiles; tl += gridDim.x * WAVES) {
     const int s0 = tl * 32, smp = s0 + c;
@@ -143,44 +89,44 @@ __global__ void __launch_bounds__(64 * WAVES, 2) trpo_kernel(const float* __rest
       const int sm = s0 + 16 * h + s;
       xt[s] = c < D ? (sm < n ? obs[(size_t)sm * D + c] : 0.0f) : (c == D ? 1.0f : 0.0f);
     }
-    v16f h1 = bias_tile(0);
-    aop(Q_W1, aw);
+    v16f h1 = bias_tile(sbias[0], h);
+    aop(wimg, Q_W1, lane, aw);
 #pragma unroll
-    for (int s = 0; s < KS1; s++) h1 = TRPO_MFMA(aw[s], xb[s], h1);
+    for (int s = 0; s < KS1; s++) h1 = TILE_MFMA(aw[s], xb[s], h1);
     v16f wt;   // cotangent on the mean, rows a = v + 4 h in registers v = 0 .. 3
     v16f d1;
     if (FVP) {
-      d1 = bias_tile(2);
-      aop(Q_DW1, aw);
+      d1 = bias_tile(sbias[2], h);
+      aop(wimg, Q_DW1, lane, aw);
 #pragma unroll
-      for (int s = 0; s < KS1; s++) d1 = TRPO_MFMA(aw[s], xb[s], d1);
+      for (int s = 0; s < KS1; s++) d1 = TILE_MFMA(aw[s], xb[s], d1);
     }
 #pragma unroll
     for (int v = 0; v < 16; v++) h1[v] = tanh_fast(h1[v]);
-    v16f h2 = bias_tile(1);
-    aop(Q_W2, aw);
+    v16f h2 = bias_tile(sbias[1], h);
+    aop(wimg, Q_W2, lane, aw);
 #pragma unroll
-    for (int v = 0; v < 16; v++) h2 = TRPO_MFMA(aw[v], h1[v], h2);
+    for (int v = 0; v < 16; v++) h2 = TILE_MFMA(aw[v], h1[v], h2);
     if (FVP) {
-      v16f d2 = bias_tile(3);
+      v16f d2 = bias_tile(sbias[3], h);
 #pragma unroll
       for (int v = 0; v < 16; v++) d1[v] *= 1.0f - h1[v] * h1[v];
 #pragma unroll
-      for (int v = 0; v < 16; v++) d2 = TRPO_MFMA(aw[v], d1[v], d2);   // W2 dH1
-      aop(Q_DW2, aw);
+      for (int v = 0; v < 16; v++) d2 = TILE_MFMA(aw[v], d1[v], d2);   // W2 dH1
+      aop(wimg, Q_DW2, lane, aw);
 #pragma unroll
-      for (int v = 0; v < 16; v++) d2 = TRPO_MFMA(aw[v], h1[v], d2);   // + dW2 H1
+      for (int v = 0; v < 16; v++) d2 = TILE_MFMA(aw[v], h1[v], d2);   // + dW2 H1
 #pragma unroll
       for (int v = 0; v < 16; v++) h2[v] = tanh_fast(h2[v]);
-      v16f dm = bias_tile(4);
-      aop(Q_DW3, aw);
+      v16f dm = bias_tile(sbias[4], h);
+      aop(wimg, Q_DW3, lane, aw);
 #pragma unroll
-      for (int v = 0; v < 16; v++) dm = TRPO_MFMA(aw[v], h2[v], dm);
+      for (int v = 0; v < 16; v++) dm = TILE_MFMA(aw[v], h2[v], dm);
 #pragma unroll
       for (int v = 0; v < 16; v++) d2[v] *= 1.0f - h2[v] * h2[v];
-      aop(Q_W3, aw);
+      aop(wimg, Q_W3, lane, aw);
 #pragma unroll
-      for (int v = 0; v < 16; v++) dm = TRPO_MFMA(aw[v], d2[v], dm);
+      for (int v = 0; v < 16; v++) dm = TILE_MFMA(aw[v], d2[v], dm);
 #pragma unroll
       for (int v = 0; v < 16; v++) wt[v] = (v < 4 && valid) ? dm[v] * pr[v] : 0.0f;
     } else {
@@ -189,55 +135,9 @@ __global__ void __launch_bounds__(64 * WAVES, 2) trpo_kernel(const float* __rest
 #pragma unroll
       for (int v = 0; v < 16; v++) wt[v] = (v < 4 && valid && v + 4 * h < A) ? wext[(size_t)smp * A + v + 4 * h] : 0.0f;
     }
-    // reverse mode: G2 = (W3' w) o (1 - H2^2), G1 = (W2' G2) o (1 - H1^2)
-    v16f g2, g1;
-#pragma unroll
-    for (int v = 0; v < 16; v++) { g2[v] = 0.0f; g1[v] = 0.0f; }
-    {
-      const float4 w = wimg[Q_W3T][lane];
-      g2 = TRPO_MFMA(w.x, wt[0], g2); g2 = TRPO_MFMA(w.y, wt[1], g2); g2 = TRPO_MFMA(w.z, wt[2], g2); g2 = TRPO_MFMA(w.w, wt[3], g2);
-    }
-#pragma unroll
-    for (int v = 0; v < 16; v++) g2[v] *= 1.0f - h2[v] * h2[v];
-    aop(Q_W2T, aw);
-#pragma unroll
-    for (int v = 0; v < 16; v++) g1 = TRPO_MFMA(aw[v], g2[v], g1);
-#pragma unroll
-    for (int v = 0; v < 16; v++) g1[v] *= 1.0f - h1[v] * h1[v];
-    // ---- parameter gradients: products over the sample index, operands transposed through the wavefront's LDS tiles
-    float ta[16], tb[16];
-    put(t0, g2); put(t1, h1);
-    wave_lds_sync();
-    get(t0, ta); get(t1, tb);
-    wave_lds_sync();
-#pragma unroll
-    for (int s = 0; s < 16; s++) { gW2 = TRPO_MFMA(ta[s], tb[s], gW2); gb2 += ta[s]; }
-    put(t0, g1);
-    wave_lds_sync();
-    get(t0, ta);
-    wave_lds_sync();
-#pragma unroll
-    for (int s = 0; s < 16; s++) gW1 = TRPO_MFMA(ta[s], xt[s], gW1);
-    put(t0, wt); put(t1, h2);
-    wave_lds_sync();
-    get(t0, ta); get(t1, tb);
-    wave_lds_sync();
-#pragma unroll
-    for (int s = 0; s < 16; s++) { gW3 = TRPO_MFMA(ta[s], tb[s], gW3); gb3 += ta[s]; }
+    reverse_tile(wimg, Q_W2T, Q_W3T, h1, h2, wt, xt, t0, t1, lane, c, h, g);
   }
-  // ---- one row of partial sums per wavefront: gW[r(v, h)][c] in register v
-  float* out = partial + (size_t)(blockIdx.x * WAVES + wave) * S::NP;
-#pragma unroll
-  for (int v = 0; v < 16; v++) {
-    const int r = (v & 3) + 8 * (v >> 2) + 4 * h;
-    out[S::O_W2 + r * H + c] = gW2[v];
-    if (c < D) out[S::O_W1 + r * D + c] = gW1[v];
-    if (c == D) out[S::O_B1 + r] = gW1[v];
-    if (r < A) out[S::O_W3 + r * H + c] = gW3[v];
-  }
-  gb2 += __shfl_xor(gb2, 32, 64); gb3 += __shfl_xor(gb3, 32, 64);
-  if (h == 0) out[S::O_B2 + c] = gb2;
-  if (h == 0 && c < A) out[S::O_B3 + c] = gb3;
+  store_row<D, A>(g, partial + (size_t)(blockIdx.x * WAVES + wave) * S::NP, c, h);   // one row of partial sums per wavefront
 }
 
 // Line search of the TRPO step (rllab's f_loss / f_constraint on the sampled batch): surrogate loss terms -exp(ll_new - ll_old) adv and
@@ -256,7 +156,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) surrogate_kernel(const float* _
   for (int s = 0; s < KS1; s++) { const int k = 2 * s + h; aW1[s] = k < D ? th.W1[c * D + k] : 0.0f; }
 #pragma unroll
   for (int v = 0; v < 16; v++) {
-    const int r = (v & 3) + 8 * (v >> 2) + 4 * h;
+    const int r = row_of(v, h);
     aW2[v] = th.W2[c * H + r];
     aW3[v] = c < A ? th.W3[c * H + r] : 0.0f;
   }
@@ -269,15 +169,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) surrogate_kernel(const float* _
     kden[v] = 1.0f / (2.0f * sn * sn + 1e-8f); kvar[v] = so * so - sn * sn;
   }
   __syncthreads();
-  auto bias_tile = [&](int which) {
-    v16f z;
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-      const float4 b = *reinterpret_cast<const float4*>(&sbias[which][8 * g + 4 * h]);
-      z[4 * g] = b.x; z[4 * g + 1] = b.y; z[4 * g + 2] = b.z; z[4 * g + 3] = b.w;
-    }
-    return z;
-  };
+  auto bias = [&](int which) { return bias_tile(sbias[which], h); };
   double accL = 0.0, accK = 0.0;
   const int ntiles = (n + 31) / 32;
   for (int tl = blockIdx.x * WAVES + wave; tl < ntiles; tl += gridDim.x * WAVES) {
@@ -293,19 +185,19 @@ __global__ void __launch_bounds__(64 * WAVES, 1) surrogate_kernel(const float* _
       ac[v] = on ? act[(size_t)smp * A + v + 4 * h] : 0.0f; om[v] = on ? old_mean[(size_t)smp * A + v + 4 * h] : 0.0f;
     }
     const float ad = valid ? adv[smp] : 0.0f;
-    v16f h1 = bias_tile(0);
+    v16f h1 = bias(0);
 #pragma unroll
-    for (int s = 0; s < KS1; s++) h1 = TRPO_MFMA(aW1[s], xb[s], h1);
+    for (int s = 0; s < KS1; s++) h1 = TILE_MFMA(aW1[s], xb[s], h1);
 #pragma unroll
     for (int v = 0; v < 16; v++) h1[v] = tanh_fast(h1[v]);
-    v16f h2 = bias_tile(1);
+    v16f h2 = bias(1);
 #pragma unroll
-    for (int v = 0; v < 16; v++) h2 = TRPO_MFMA(aW2[v], h1[v], h2);
+    for (int v = 0; v < 16; v++) h2 = TILE_MFMA(aW2[v], h1[v], h2);
 #pragma unroll
     for (int v = 0; v < 16; v++) h2[v] = tanh_fast(h2[v]);
-    v16f mu = bias_tile(2);
+    v16f mu = bias(2);
 #pragma unroll
-    for (int v = 0; v < 16; v++) mu = TRPO_MFMA(aW3[v], h2[v], mu);
+    for (int v = 0; v < 16; v++) mu = TILE_MFMA(aW3[v], h2[v], mu);
     float ll = 0.0f, kl = 0.0f;
 #pragma unroll
     for (int v = 0; v < 4; v++) {
@@ -390,7 +282,7 @@ __global__ void __launch_bounds__(64 * WAVES, 2) policy_step_mfma_kernel(const d
   for (int s = 0; s < KS1; s++) { const int k = 2 * s + h; aW1[s] = k < D ? th.W1[c * D + k] : 0.0f; }
 #pragma unroll
   for (int v = 0; v < 16; v++) {
-    const int r = (v & 3) + 8 * (v >> 2) + 4 * h;
+    const int r = row_of(v, h);
     aW2[v] = th.W2[c * H + r];
     aW3[v] = c < A ? th.W3[c * H + r] : 0.0f;
   }
@@ -401,15 +293,7 @@ __global__ void __launch_bounds__(64 * WAVES, 2) policy_step_mfma_kernel(const d
     lo[v] = a < A ? low[a] : 0.0; hi[v] = a < A ? high[a] : 0.0;
   }
   __syncthreads();
-  auto bias_tile = [&](int which) {
-    v16f z;
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-      const float4 b = *reinterpret_cast<const float4*>(&sbias[which][8 * g + 4 * h]);
-      z[4 * g] = b.x; z[4 * g + 1] = b.y; z[4 * g + 2] = b.z; z[4 * g + 3] = b.w;
-    }
-    return z;
-  };
+  auto bias = [&](int which) { return bias_tile(sbias[which], h); };
   const int ntiles = (n + 31) / 32;
   for (int tl = blockIdx.x * WAVES + wave; tl < ntiles; tl += gridDim.x * WAVES) {
     const int smp = tl * 32 + c;
@@ -422,19 +306,19 @@ __global__ void __launch_bounds__(64 * WAVES, 2) policy_step_mfma_kernel(const d
       xb[s] = on ? (float)obs[(size_t)smp * D + k] : 0.0f;
       if (on) obs32[(size_t)smp * D + k] = xb[s];
     }
-    v16f h1 = bias_tile(0);
+    v16f h1 = bias(0);
 #pragma unroll
-    for (int s = 0; s < KS1; s++) h1 = TRPO_MFMA(aW1[s], xb[s], h1);
+    for (int s = 0; s < KS1; s++) h1 = TILE_MFMA(aW1[s], xb[s], h1);
 #pragma unroll
     for (int v = 0; v < 16; v++) h1[v] = tanh_fast(h1[v]);
-    v16f h2 = bias_tile(1);
+    v16f h2 = bias(1);
 #pragma unroll
-    for (int v = 0; v < 16; v++) h2 = TRPO_MFMA(aW2[v], h1[v], h2);
+    for (int v = 0; v < 16; v++) h2 = TILE_MFMA(aW2[v], h1[v], h2);
 #pragma unroll
     for (int v = 0; v < 16; v++) h2[v] = tanh_fast(h2[v]);
-    v16f mu = bias_tile(2);
+    v16f mu = bias(2);
 #pragma unroll
-    for (int v = 0; v < 16; v++) mu = TRPO_MFMA(aW3[v], h2[v], mu);
+    for (int v = 0; v < 16; v++) mu = TILE_MFMA(aW3[v], h2[v], mu);
 #pragma unroll
     for (int v = 0; v < 4; v++) {
       const int a = v + 4 * h;
@@ -481,79 +365,11 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(const double* __restr
   if (threadIdx.x == 0) { partial[2 * blockIdx.x] = red[0][0]; partial[2 * blockIdx.x + 1] = red[1][0]; }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- CG vector step
-// What rllab's conjugate gradient (rllab/misc/krylov.py: cg) does between two Fisher-vector products, on the ~2 k-entry parameter
-// vector, in one workgroup: F p from the mean network's part (summed over wavefronts and ranks by the caller) + the log-std block +
-// the damping, step length, x and r updates, new residual, early exit as a frozen step length (no host read-back), new direction.
-// As torch operations: ~15 launches per iteration, a third of what an iteration costs next to the 0.12 ms product.
-__device__ __forceinline__ float block_sum_1024(float v, float* red) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float t = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 16; i++) t += red[i];   // every thread adds the 16 wavefront sums in the same order
-  return t;
-}
-__global__ void __launch_bounds__(1024) cg_update_kernel(int n, int ls_off, int n_ls, const float* __restrict__ Apm, const float* __restrict__ hls, float reg,
-                                                        float tol, float* __restrict__ x, float* __restrict__ r, float* __restrict__ p, float* __restrict__ scal) {
-  __shared__ float red[16];
-  constexpr int PER = 3;   // n <= 3072
-  float pv[PER], ap[PER], rv[PER];
-  float s = 0.0f;
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    const int i = threadIdx.x + 1024 * k;
-    pv[k] = 0.0f; ap[k] = 0.0f; rv[k] = 0.0f;
-    if (i < n) {
-      pv[k] = p[i]; rv[k] = r[i];
-      const bool ls = i >= ls_off && i < ls_off + n_ls;
-      const float f = ls ? hls[i - ls_off] * pv[k] : Apm[i < ls_off ? i : i - n_ls];
-      ap[k] = f + reg * pv[k];
-      s += pv[k] * ap[k];
-    }
-  }
-  const float pAp = block_sum_1024(s, red);
-  const float rr = scal[0];
-  const bool running = scal[1] != 0.0f;
-  const float alpha = running ? rr / pAp : 0.0f;
-  s = 0.0f;
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    const int i = threadIdx.x + 1024 * k;
-    if (i < n) { x[i] += alpha * pv[k]; rv[k] -= alpha * ap[k]; r[i] = rv[k]; s += rv[k] * rv[k]; }
-  }
-  const float rr_new = block_sum_1024(s, red);
-  const bool go_on = running && rr_new >= tol;
-  const float beta = go_on ? rr_new / rr : 0.0f;
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    const int i = threadIdx.x + 1024 * k;
-    if (i < n) p[i] = rv[k] + beta * pv[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) { scal[0] = rr_new; scal[1] = go_on ? 1.0f : 0.0f; }
-}
-
-inline int blocks_for(int n) {
-  const int tiles = (n + 31) / 32;
-  int b = (tiles + WAVES - 1) / WAVES;
-  return b < 1 ? 1 : (b > MAX_BLOCKS ? MAX_BLOCKS : b);
-}
-
 template <bool FVP>
 int launch(const float* obs, int n, int D, int A, const Net& th, const Net& dir, const float* prec, float scale, const float* wext, float* partial, hipStream_t s) {
   if (!obs || n <= 0 || !partial) return CASSIE_EINVAL;
   const dim3 grid(blocks_for(n)), block(64 * WAVES);
-  if (D == 26 && A == 6) hipLaunchKernelGGL((trpo_kernel<26, 6, FVP>), grid, block, 0, s, obs, n, th, dir, prec, scale, wext, partial);
-  else if (D == 26 && A == 7) hipLaunchKernelGGL((trpo_kernel<26, 7, FVP>), grid, block, 0, s, obs, n, th, dir, prec, scale, wext, partial);
-  else if (D == 17 && A == 6) hipLaunchKernelGGL((trpo_kernel<17, 6, FVP>), grid, block, 0, s, obs, n, th, dir, prec, scale, wext, partial);
-  else if (D == 17 && A == 7) hipLaunchKernelGGL((trpo_kernel<17, 7, FVP>), grid, block, 0, s, obs, n, th, dir, prec, scale, wext, partial);
-  else return CASSIE_EINVAL;
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  return launch_shape(D, A, [&](auto d, auto a) { hipLaunchKernelGGL((trpo_kernel<d(), a(), FVP>), grid, block, 0, s, obs, n, th, dir, prec, scale, wext, partial); });
 }
 
 }  // namespace cassie_trpo
@@ -569,40 +385,35 @@ int CassieTrpoPartialRows(int n_samples) { return cassie_trpo::blocks_for(n_samp
 int CassieTrpoFvp(const float* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2,
                   const float* W3, const float* b3, const float* dW1, const float* db1, const float* dW2, const float* db2, const float* dW3,
                   const float* db3, const float* prec, float scale, float* partial_dev, void* stream) {
-  if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !dW1 || !db1 || !dW2 || !db2 || !dW3 || !db3 || !prec) return CASSIE_EINVAL;
   const cassie_trpo::Net th{W1, b1, W2, b2, W3, b3}, dir{dW1, db1, dW2, db2, dW3, db3};
+  if (!net_ok(th) || !net_ok(dir) || !prec) return CASSIE_EINVAL;
   return cassie_trpo::launch<true>(obs_dev, n, obs_dim, act_dim, th, dir, prec, scale, nullptr, partial_dev, (hipStream_t)stream);
 }
 
 int CassieTrpoVjp(const float* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2,
                   const float* W3, const float* b3, const float* w_dev, float* partial_dev, void* stream) {
-  if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !w_dev) return CASSIE_EINVAL;
   const cassie_trpo::Net th{W1, b1, W2, b2, W3, b3};
+  if (!net_ok(th) || !w_dev) return CASSIE_EINVAL;
   return cassie_trpo::launch<false>(obs_dev, n, obs_dim, act_dim, th, th, nullptr, 0.0f, w_dev, partial_dev, (hipStream_t)stream);
 }
 
 int CassieTrpoSurrogate(const float* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2,
                         const float* W3, const float* b3, const float* log_std_new, const float* log_std_old, const float* act_dev,
                         const float* adv_dev, const float* old_mean_dev, double* partial_dev, void* stream) {
-  if (!obs_dev || n <= 0 || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !log_std_new || !log_std_old || !act_dev || !adv_dev || !old_mean_dev || !partial_dev)
-    return CASSIE_EINVAL;
-  const cassie_trpo::Net th{W1, b1, W2, b2, W3, b3};
-  const dim3 grid(cassie_trpo::blocks_for(n)), block(64 * cassie_trpo::WAVES);
-  hipStream_t s = (hipStream_t)stream;
   using namespace cassie_trpo;
-  if (obs_dim == 26 && act_dim == 6) hipLaunchKernelGGL((surrogate_kernel<26, 6>), grid, block, 0, s, obs_dev, n, th, log_std_new, log_std_old, act_dev, adv_dev, old_mean_dev, partial_dev);
-  else if (obs_dim == 26 && act_dim == 7) hipLaunchKernelGGL((surrogate_kernel<26, 7>), grid, block, 0, s, obs_dev, n, th, log_std_new, log_std_old, act_dev, adv_dev, old_mean_dev, partial_dev);
-  else if (obs_dim == 17 && act_dim == 6) hipLaunchKernelGGL((surrogate_kernel<17, 6>), grid, block, 0, s, obs_dev, n, th, log_std_new, log_std_old, act_dev, adv_dev, old_mean_dev, partial_dev);
-  else if (obs_dim == 17 && act_dim == 7) hipLaunchKernelGGL((surrogate_kernel<17, 7>), grid, block, 0, s, obs_dev, n, th, log_std_new, log_std_old, act_dev, adv_dev, old_mean_dev, partial_dev);
-  else return CASSIE_EINVAL;
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  const Net th{W1, b1, W2, b2, W3, b3};
+  if (!obs_dev || n <= 0 || !net_ok(th) || !log_std_new || !log_std_old || !act_dev || !adv_dev || !old_mean_dev || !partial_dev) return CASSIE_EINVAL;
+  return launch_shape(obs_dim, act_dim, [&](auto d, auto a) {
+    hipLaunchKernelGGL((surrogate_kernel<d(), a()>), dim3(blocks_for(n)), dim3(64 * WAVES), 0, (hipStream_t)stream, obs_dev, n, th, log_std_new, log_std_old, act_dev,
+                       adv_dev, old_mean_dev, partial_dev);
+  });
 }
 
 int CassieTrpoCgUpdate(int n, int ls_off, int n_ls, const float* Ap_mean_dev, const float* hls_dev, float reg, float tol, float* x_dev, float* r_dev, float* p_dev,
                        float* scal_dev, void* stream) {
   if (n <= 0 || n > 3072 || ls_off < 0 || n_ls < 0 || ls_off + n_ls > n || !Ap_mean_dev || !hls_dev || !x_dev || !r_dev || !p_dev || !scal_dev) return CASSIE_EINVAL;
-  hipLaunchKernelGGL(cassie_trpo::cg_update_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, ls_off, n_ls, Ap_mean_dev, hls_dev, reg, tol, x_dev, r_dev, p_dev, scal_dev);
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  hipLaunchKernelGGL(cassie_onpolicy::cg_update_kernel<3>, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, ls_off, n_ls, Ap_mean_dev, hls_dev, reg, tol, x_dev, r_dev, p_dev, scal_dev);
+  return cassie_tiles::launched();
 }
 
 int CassieTrpoSamplerRows(int n_envs) { return n_envs > 0 ? (n_envs + 255) / 256 : 0; }
@@ -612,32 +423,27 @@ int CassieTrpoSamplerStep(const double* rew_dev, const unsigned char* done_dev, 
   if (!rew_dev || !done_dev || n <= 0 || !path_t_dev || !path_ret_dev || !rew_row_dev || !t_row_dev || !cut_row_dev || !partial_dev) return CASSIE_EINVAL;
   hipLaunchKernelGGL(cassie_trpo::sampler_step_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, rew_dev, done_dev, n, max_path_length, path_t_dev,
                      path_ret_dev, rew_row_dev, t_row_dev, cut_row_dev, partial_dev);
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  return cassie_tiles::launched();
 }
 
 int CassieTrpoPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2,
                          const float* b2, const float* W3, const float* b3, const float* log_std, const float* noise_dev,
                          const double* low_dev, const double* high_dev, float* obs32_dev, float* mean_dev, float* act_dev,
                          double* env_actions_dev, void* stream) {
-  if (!obs_dev || n <= 0 || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !log_std || !noise_dev || !low_dev || !high_dev || !obs32_dev || !mean_dev ||
-      !act_dev || !env_actions_dev)
-    return CASSIE_EINVAL;
-  const cassie_trpo::Net th{W1, b1, W2, b2, W3, b3};
-  hipStream_t s = (hipStream_t)stream;
   using namespace cassie_trpo;
+  const Net th{W1, b1, W2, b2, W3, b3};
+  if (!obs_dev || n <= 0 || !net_ok(th) || !log_std || !noise_dev || !low_dev || !high_dev || !obs32_dev || !mean_dev || !act_dev || !env_actions_dev)
+    return CASSIE_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
   static const bool vector_path = [] { const char* e = getenv("CASSIE_TRPO_POLICY_VALU"); return e && e[0] == '1'; }();   // the one-lane-per-environment kernel (A/B, tests)
-  if (vector_path) {
-    const dim3 grid((n + 255) / 256), block(256);
-    if (obs_dim == 26 && act_dim == 6) hipLaunchKernelGGL((policy_step_kernel<26, 6>), grid, block, 0, s, obs_dev, n, th, log_std, noise_dev, low_dev, high_dev, obs32_dev, mean_dev, act_dev, env_actions_dev);
-    else if (obs_dim == 26 && act_dim == 7) hipLaunchKernelGGL((policy_step_kernel<26, 7>), grid, block, 0, s, obs_dev, n, th, log_std, noise_dev, low_dev, high_dev, obs32_dev, mean_dev, act_dev, env_actions_dev);
-    else return CASSIE_EINVAL;
-    return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
-  }
-  const dim3 grid(blocks_for(n)), block(64 * WAVES);
-  if (obs_dim == 26 && act_dim == 6) hipLaunchKernelGGL((policy_step_mfma_kernel<26, 6>), grid, block, 0, s, obs_dev, n, th, log_std, noise_dev, low_dev, high_dev, obs32_dev, mean_dev, act_dev, env_actions_dev);
-  else if (obs_dim == 26 && act_dim == 7) hipLaunchKernelGGL((policy_step_mfma_kernel<26, 7>), grid, block, 0, s, obs_dev, n, th, log_std, noise_dev, low_dev, high_dev, obs32_dev, mean_dev, act_dev, env_actions_dev);
-  else return CASSIE_EINVAL;
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  return launch_shape<true>(obs_dim, act_dim, [&](auto d, auto a) {
+    if (vector_path)
+      hipLaunchKernelGGL((policy_step_kernel<d(), a()>), dim3((n + 255) / 256), dim3(256), 0, s, obs_dev, n, th, log_std, noise_dev, low_dev, high_dev, obs32_dev, mean_dev,
+                         act_dev, env_actions_dev);
+    else
+      hipLaunchKernelGGL((policy_step_mfma_kernel<d(), a()>), dim3(blocks_for(n)), dim3(64 * WAVES), 0, s, obs_dev, n, th, log_std, noise_dev, low_dev, high_dev, obs32_dev,
+                         mean_dev, act_dev, env_actions_dev);
+  });
 }
 
 }  // extern "C"

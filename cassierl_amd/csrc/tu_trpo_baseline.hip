@@ -20,6 +20,7 @@
 
 #include "../../include/cassie_trpo.h"
 #include "../../include/cassie_vec.h"
+#include "cassie_onpolicy.h"   // clip10, path_clock (shared with tu_ppo.hip's GAE)
 
 namespace cassie_trpo {
 
@@ -33,9 +34,8 @@ template <int D> struct Feat {
   static constexpr int NBLK = NB * (NB + 1) / 2;
 };
 
-__device__ __forceinline__ float clip10(float x) { return fminf(fmaxf(x, -10.0f), 10.0f); }
-// t / 100 as torch evaluates `t.to(float32) / 100.0` on the device: a multiplication by the float32 reciprocal of the scalar
-__device__ __forceinline__ float path_clock(long long t) { return (float)t * (1.0f / 100.0f); }
+using cassie_onpolicy::clip10;
+using cassie_onpolicy::path_clock;
 
 // column F of Z for one sample (obs row `o`, path clock t, target y); compile-time block r, run-time f
 template <int D>
@@ -230,23 +230,20 @@ int CassieTrpoGramRowSize(int obs_dim) {
 
 int CassieTrpoBaselineGram(const float* obs_dev, const long long* t_dev, const double* y_dev, int m, int obs_dim, double* partial_dev, void* stream) {
   if (!obs_dev || !t_dev || !y_dev || m <= 0 || !partial_dev) return CASSIE_EINVAL;
-  const dim3 grid(cassie_trpo::GRAM_BLOCKS), block(64 * cassie_trpo::GRAM_WAVES);
-  if (obs_dim == 26) hipLaunchKernelGGL(cassie_trpo::gram_kernel<26>, grid, block, 0, (hipStream_t)stream, obs_dev, t_dev, y_dev, m, partial_dev);
-  else if (obs_dim == 17) hipLaunchKernelGGL(cassie_trpo::gram_kernel<17>, grid, block, 0, (hipStream_t)stream, obs_dev, t_dev, y_dev, m, partial_dev);
-  else return CASSIE_EINVAL;
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  using namespace cassie_trpo;
+  return cassie_tiles::launch_obs(obs_dim, [&](auto d) {
+    hipLaunchKernelGGL(gram_kernel<d()>, dim3(GRAM_BLOCKS), dim3(64 * GRAM_WAVES), 0, (hipStream_t)stream, obs_dev, t_dev, y_dev, m, partial_dev);
+  });
 }
 
 int CassieTrpoReturnsAdvantages(const float* obs_dev, const long long* t_dev, const double* rew_dev, const unsigned char* cut_dev, int T, int n, int obs_dim,
                                 const double* coeffs_dev, const double* last_value_dev, double gamma, double* returns_dev, double* adv_dev, double* partial_dev,
                                 void* stream) {
   if (!obs_dev || !t_dev || !rew_dev || !cut_dev || T <= 0 || n <= 0 || !returns_dev || !adv_dev || !partial_dev) return CASSIE_EINVAL;
-  const dim3 grid((n + 255) / 256), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (obs_dim == 26) hipLaunchKernelGGL(cassie_trpo::returns_adv_kernel<26>, grid, block, 0, s, obs_dev, t_dev, rew_dev, cut_dev, T, n, coeffs_dev, last_value_dev, gamma, returns_dev, adv_dev, partial_dev);
-  else if (obs_dim == 17) hipLaunchKernelGGL(cassie_trpo::returns_adv_kernel<17>, grid, block, 0, s, obs_dev, t_dev, rew_dev, cut_dev, T, n, coeffs_dev, last_value_dev, gamma, returns_dev, adv_dev, partial_dev);
-  else return CASSIE_EINVAL;
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  return cassie_tiles::launch_obs(obs_dim, [&](auto d) {
+    hipLaunchKernelGGL(cassie_trpo::returns_adv_kernel<d()>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, obs_dev, t_dev, rew_dev, cut_dev, T, n, coeffs_dev,
+                       last_value_dev, gamma, returns_dev, adv_dev, partial_dev);
+  });
 }
 
 int CassieTrpoRidgeSolve(const double* A_dev, const double* b_dev, int F, double reg, double* x_dev, void* stream) {
@@ -254,16 +251,14 @@ int CassieTrpoRidgeSolve(const double* A_dev, const double* b_dev, int F, double
   if (F == 56) hipLaunchKernelGGL(cassie_trpo::ridge_solve_kernel<56>, dim3(1), dim3(64), 0, (hipStream_t)stream, A_dev, b_dev, reg, x_dev);
   else if (F == 38) hipLaunchKernelGGL(cassie_trpo::ridge_solve_kernel<38>, dim3(1), dim3(64), 0, (hipStream_t)stream, A_dev, b_dev, reg, x_dev);
   else return CASSIE_EINVAL;
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  return cassie_tiles::launched();
 }
 
 int CassieTrpoBaselinePredict(const float* obs_dev, const long long* t_dev, int m, int obs_dim, const double* coeffs_dev, double* out_dev, void* stream) {
   if (!obs_dev || !t_dev || m <= 0 || !coeffs_dev || !out_dev) return CASSIE_EINVAL;
-  const dim3 grid((m + 255) / 256), block(256);
-  if (obs_dim == 26) hipLaunchKernelGGL(cassie_trpo::predict_kernel<26>, grid, block, 0, (hipStream_t)stream, obs_dev, t_dev, m, coeffs_dev, out_dev);
-  else if (obs_dim == 17) hipLaunchKernelGGL(cassie_trpo::predict_kernel<17>, grid, block, 0, (hipStream_t)stream, obs_dev, t_dev, m, coeffs_dev, out_dev);
-  else return CASSIE_EINVAL;
-  return hipGetLastError() == hipSuccess ? CASSIE_OK : CASSIE_EHIP;
+  return cassie_tiles::launch_obs(obs_dim, [&](auto d) {
+    hipLaunchKernelGGL(cassie_trpo::predict_kernel<d()>, dim3((m + 255) / 256), dim3(256), 0, (hipStream_t)stream, obs_dev, t_dev, m, coeffs_dev, out_dev);
+  });
 }
 
 }  // extern "C"
