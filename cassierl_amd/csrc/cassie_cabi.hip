@@ -21,6 +21,10 @@
 
 namespace cassie {
 constexpr int NSLOT = CP_NSLOT;
+}
+// words of the phase-clock buffer: the 64-environments-per-wavefront kernel has 24 buckets (leg::DUO_PHASES), the other kernels use the first 16
+constexpr int CASSIE_PHASE_WORDS = 24;
+namespace cassie {
 namespace launch {
 // the physics launchers (cassie_launch.h): the tier's height-field instantiation when the parameters carry a terrain library
 void step_k1(int mode, K1Variant variant, int n_envs, hipStream_t s, const VecParams& p, int split) {
@@ -75,7 +79,7 @@ struct CassieVec {
   size_t duo_ws_bytes = 0;
   int duo_envs = 0;                          // environments [0, duo_envs) take that form, the rest the two-lanes kernel (0 or n unless the size rule splits the batch)
   bool duo = false;                          // ... in its 64-environments-per-wavefront form (cassie_kernels_duo.hip; CASSIE2D_DUO=0/1 overrides the size rule)
-  unsigned long long* phase = nullptr;       // profiling builds (-DCASSIE_PHASE_TIMING): 16 cycle accumulators
+  unsigned long long* phase = nullptr;       // profiling builds (-DCASSIE_PHASE_TIMING): CASSIE_PHASE_WORDS cycle accumulators
   unsigned long long* stats = nullptr;       // device event counters (cassie::STAT_*)
   unsigned long long substeps_requested = 0; // host: env-substeps asked for since the counters were last cleared
   bool g16 = true;                           // CASSIE2D_G16=0 selects the wave-per-environment kernel only (A/B)
@@ -424,8 +428,8 @@ int CassieVecCreate(CassieVec** out, int n_envs, int device, const CassieVecConf
   if (hipMalloc(&h->pending_leg, n * sizeof(int)) != hipSuccess) return bail(CASSIE_EHIP);
   if (hipMemset(h->pending_leg, 0, n * sizeof(int)) != hipSuccess) return bail(CASSIE_EHIP);
 #ifdef CASSIE_PHASE_TIMING
-  if (hipMalloc(&h->phase, 16 * sizeof(unsigned long long)) != hipSuccess) return bail(CASSIE_EHIP);
-  if (hipMemset(h->phase, 0, 16 * sizeof(unsigned long long)) != hipSuccess) return bail(CASSIE_EHIP);
+  if (hipMalloc(&h->phase, CASSIE_PHASE_WORDS * sizeof(unsigned long long)) != hipSuccess) return bail(CASSIE_EHIP);
+  if (hipMemset(h->phase, 0, CASSIE_PHASE_WORDS * sizeof(unsigned long long)) != hipSuccess) return bail(CASSIE_EHIP);
 #endif
   if (hipMalloc(&h->stats, cassie::STAT_N * sizeof(unsigned long long)) != hipSuccess) return bail(CASSIE_EHIP);
   if (hipMemset(h->stats, 0, cassie::STAT_N * sizeof(unsigned long long)) != hipSuccess) return bail(CASSIE_EHIP);
@@ -464,6 +468,8 @@ int CassieVecCreate(CassieVec** out, int n_envs, int device, const CassieVecConf
   { const char* e = getenv("CASSIE2D_DUO"); if (e && (e[0] == '0' || e[0] == '1')) h->duo_envs = (h->leg && e[0] == '1') ? n_envs : 0; }
   if (h->cfg.flags & CASSIE_DUO_TIER_OFF) h->duo_envs = 0;
   if (h->cfg.flags & CASSIE_DUO_TIER_ON) h->duo_envs = h->leg ? n_envs : 0;
+  // that kernel addresses the batch arrays with 32-bit byte offsets (cassie_kernels_duo.hip: duo_io); a batch whose records exceed 4 GiB (6.1 M envs) stays in the pair form
+  if ((unsigned long long)n_envs * cassie::ENV_STRIDE * sizeof(double) > 0xFFFFFFFFull) h->duo_envs = 0;
   h->duo = h->duo_envs > 0;
   if (h->duo) {
     h->duo_table = L2::duo_table_slots(h->duo_envs, simds);
@@ -592,11 +598,11 @@ extern "C" int CassieVecPhaseMode() {  // what CassieVecPhaseCycles counts: 1 th
   return 1;
 #endif
 }
-extern "C" int CassieVecPhaseCycles(CassieVec* h, unsigned long long* out16) {  // profiling builds only; not part of the public ABI
+extern "C" int CassieVecPhaseCycles(CassieVec* h, unsigned long long* out24) {  // profiling builds only; not part of the public ABI
   if (!h || !h->phase) return CASSIE_EINVAL;
   if (hipStreamSynchronize(h->stream) != hipSuccess) return CASSIE_EHIP;
-  if (hipMemcpy(out16, h->phase, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return CASSIE_EHIP;
-  hipMemset(h->phase, 0, 16 * sizeof(unsigned long long));
+  if (hipMemcpy(out24, h->phase, CASSIE_PHASE_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return CASSIE_EHIP;
+  hipMemset(h->phase, 0, CASSIE_PHASE_WORDS * sizeof(unsigned long long));
   return CASSIE_OK;
 }
 #endif

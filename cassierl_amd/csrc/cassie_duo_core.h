@@ -663,35 +663,42 @@ template <class B> struct Duo : Core<B> {
     const M left = leg == 0;
     const M none = left & !left;
     M live[2];
-    lfor<0, 2>([&](auto gg) {
-      constexpr int G = decltype(gg)::value;
-      const Io io = io_of(G);
-      lds.select(G, io);
-      Lane st;
-      lfor<0, 3>([&](auto bb) {
-        constexpr int Bc = decltype(bb)::value;
-        st.qb[Bc] = B::pld(io.rec, I(ES_Q + Bc)); st.vb[Bc] = B::pld(io.rec, I(ES_V + Bc)); st.wb[Bc] = B::pld(io.rec, I(ES_WS + Bc));
-      });
-      lfor<0, 5>([&](auto dd) {
-        constexpr int Dd = decltype(dd)::value;
-        st.ql[Dd] = B::pld(io.rec, lo + (ES_Q + Dd)); st.vl[Dd] = B::pld(io.rec, lo + (ES_V + Dd)); st.wl[Dd] = B::pld(io.rec, lo + (ES_WS + Dd));
-      });
-      put_lane(ws, G * W_GROUP, st);
-      const M all = valid[G] | !valid[G];
-      lds.cst(C::C_TIME, B::pld(io.rec, I(ES_TIME)), all);
-      {
-        D a2own = 0.0;
+    {
+      // records in: ONE batch of loads for both groups (no load of group B behind group A's stores to the workspace), then the lane states are parked
+      Lane st[2];
+      D time0[2], a2own[2];
+      lfor<0, 2>([&](auto gg) {
+        constexpr int G = decltype(gg)::value;
+        const Io io = io_of(G);
+        lfor<0, 3>([&](auto bb) {
+          constexpr int Bc = decltype(bb)::value;
+          st[G].qb[Bc] = B::pld(io.rec, I(ES_Q + Bc)); st[G].vb[Bc] = B::pld(io.rec, I(ES_V + Bc)); st[G].wb[Bc] = B::pld(io.rec, I(ES_WS + Bc));
+        });
+        lfor<0, 5>([&](auto dd) {
+          constexpr int Dd = decltype(dd)::value;
+          st[G].ql[Dd] = B::pld(io.rec, lo + (ES_Q + Dd)); st[G].vl[Dd] = B::pld(io.rec, lo + (ES_V + Dd)); st[G].wl[Dd] = B::pld(io.rec, lo + (ES_WS + Dd));
+        });
+        time0[G] = B::pld(io.rec, I(ES_TIME));
+        a2own[G] = 0.0;
         if (io.has_act && cfg.env_kind != 0) {
-          lfor<0, 3>([&](auto aa) { constexpr int A_ = decltype(aa)::value; const D a = B::pld(io.act, ao + A_); a2own += a * a; });
-          if (cfg.adim == 7) { const D a = B::pld(io.act, I(6)); a2own += B::sel(left, a * a, D(0.0)); }
+          lfor<0, 3>([&](auto aa) { constexpr int A_ = decltype(aa)::value; const D a = B::pld(io.act, ao + A_); a2own[G] += a * a; });
+          if (cfg.adim == 7) { const D a = B::pld(io.act, I(6)); a2own[G] += B::sel(left, a * a, D(0.0)); }
         }
-        lds.cst(C::C_A2, a2own, all);
-      }
-      live[G] = valid[G];
-      o[G].set_state = none;
-      o[G].pend = 0; o[G].niter = 0;
-      o[G].do_reset = none; o[G].bad = none;
-    });
+      });
+      lfor<0, 2>([&](auto gg) {
+        constexpr int G = decltype(gg)::value;
+        const Io io = io_of(G);
+        lds.select(G, io);
+        put_lane(ws, G * W_GROUP, st[G]);
+        const M all = valid[G] | !valid[G];
+        lds.cst(C::C_TIME, time0[G], all);
+        lds.cst(C::C_A2, a2own[G], all);
+        live[G] = valid[G];
+        o[G].set_state = none;
+        o[G].pend = 0; o[G].niter = 0;
+        o[G].do_reset = none; o[G].bad = none;
+      });
+    }
     B::fence();
     lds.mark(16);   // (16..21: pieces of the glue, bucket 0) 16 = records in, state parked
     bool reset_pass = false;
@@ -888,25 +895,34 @@ template <class B> struct Duo : Core<B> {
     // ---- state write-back: q, v, warm start, clock, iteration count; the setState snapshot, the motor commands and qstate are in
     // the record already (written where they changed)
     lds.mark(20);
+    // One batch of loads (both groups' lane states, clocks), then one batch of stores under the three masks that exist (valid & left: base dofs, clock,
+    // sweep count; valid: the lane's leg; valid & left & do_reset: what a new episode clears): nothing but stores from there to the end of the kernel.
+    Lane stw[2];
+    D time1[2];
+    lfor<0, 2>([&](auto gg) {
+      constexpr int G = decltype(gg)::value;
+      lds.select(G, io_of(G));
+      get_lane(ws, G * W_GROUP, stw[G]);
+      time1[G] = lds.cld(C::C_TIME);
+    });
     lfor<0, 2>([&](auto gg) {
       constexpr int G = decltype(gg)::value;
       const Io io = io_of(G);
-      lds.select(G, io);
-      Lane st;
-      get_lane(ws, G * W_GROUP, st);
+      const Lane& st = stw[G];
+      const D nit1 = B::toD(o[G].niter);
+      const M vl = valid[G] & left, vr = vl & o[G].do_reset;
       lfor<0, 3>([&](auto bb) {
         constexpr int Bc = decltype(bb)::value;
-        const M lv = valid[G] & left;
-        B::pst(io.rec, I(ES_Q + Bc), st.qb[Bc], lv); B::pst(io.rec, I(ES_V + Bc), st.vb[Bc], lv); B::pst(io.rec, I(ES_WS + Bc), st.wb[Bc], lv);
-        B::pst(io.rec, I(ES_QSTATE + Bc), D(cp_env_qinit[Bc]), lv & o[G].do_reset);
+        B::pst(io.rec, I(ES_Q + Bc), st.qb[Bc], vl); B::pst(io.rec, I(ES_V + Bc), st.vb[Bc], vl); B::pst(io.rec, I(ES_WS + Bc), st.wb[Bc], vl);
       });
+      B::pst(io.rec, I(ES_TIME), time1[G], vl);
+      B::pst(io.rec, I(ES_NITER), nit1, vl);
       lfor<0, 5>([&](auto dd) {
         constexpr int Dd = decltype(dd)::value;
         B::pst(io.rec, lo + (ES_Q + Dd), st.ql[Dd], valid[G]); B::pst(io.rec, lo + (ES_V + Dd), st.vl[Dd], valid[G]); B::pst(io.rec, lo + (ES_WS + Dd), st.wl[Dd], valid[G]);
       });
-      B::pst(io.rec, I(ES_TIME), lds.cld(C::C_TIME), valid[G] & left);
-      B::pst(io.rec, I(ES_NITER), B::toD(o[G].niter), valid[G] & left);
-      B::pst(io.rec, I(ES_QPWSET), D(0.0), valid[G] & left & o[G].do_reset);
+      lfor<0, 3>([&](auto bb) { constexpr int Bc = decltype(bb)::value; B::pst(io.rec, I(ES_QSTATE + Bc), D(cp_env_qinit[Bc]), vr); });
+      B::pst(io.rec, I(ES_QPWSET), D(0.0), vr);
     });
     lds.mark(21);   // 21 = write-back
   }

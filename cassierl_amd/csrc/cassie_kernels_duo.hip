@@ -19,6 +19,7 @@ namespace leg {
 
 constexpr int DUO_WAVES = 2;   // independent wavefronts per workgroup (no barrier, no shared data).  A/B r05, 65 536 envs: 1 -> 1.146 ms, 2 -> 1.125, 4 -> 1.129
 #define DUO_LANE ((int)threadIdx.x & 63)
+constexpr int DUO_PHASES = 24;   // profiling builds: cycle accumulators of this kernel (CASSIE_PHASE_WORDS of cassie_cabi.hip)
 __device__ const double duo_zero_action[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // the action row of a step without actions
 struct DuoShared {
   double cold[2][20][64];    // per group: clock, a2, tau_b 3, tau_l 5, link origins x 5, z 5 (the pelvis origin is the constant 0)
@@ -62,6 +63,24 @@ struct DevDuoB : DevB {
     u32x4 w; w.x = (unsigned)__double2loint(a); w.y = (unsigned)__double2hiint(a); w.z = (unsigned)__double2loint(b); w.w = (unsigned)__double2hiint(b);
     __builtin_amdgcn_raw_buffer_store_b128(w, ws.r, ws.voff, wofs(slot), 0);
   }
+  // The batch arrays (state records, action / observation rows, reward, done flags) are addressed the same way: `P` is ONE descriptor over the whole
+  // array (wave-uniform, built from the kernel arguments where a phase needs it: scalar registers) and the byte offset of the lane's row in one
+  // VGPR.  An access costs no 64-bit per-lane pointer -- six of them per group were what the allocator spilled, and every store behind a spilled
+  // pointer waited for the pointer's reload, i.e. for every store before it (vmcnt counts stores until they are acknowledged).  num_records is the
+  // array's size in bytes: the hardware drops a store (and zeroes a load) beyond it.
+  struct P { __amdgpu_buffer_rsrc_t r; unsigned voff; };
+  typedef P P8;
+  static LEG_FN double pld(P p, int off) {
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(p.r, p.voff + (unsigned)off * 8u, 0, 0);
+    return __hiloint2double((int)v.y, (int)v.x);
+  }
+  static LEG_FN void pst(P p, int off, double v, bool m) {
+    if (m) {
+      u32x2 w; w.x = (unsigned)__double2loint(v); w.y = (unsigned)__double2hiint(v);
+      __builtin_amdgcn_raw_buffer_store_b64(w, p.r, p.voff + (unsigned)off * 8u, 0, 0);
+    }
+  }
+  static LEG_FN void pst8(P8 p, bool v, bool m) { if (m) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)v, p.r, p.voff, 0, 0); }
 #ifdef DUO_VIEW_EXPERIMENT
   // the view of joint lane 2e + k on column 2e + X of group k's block (group stride in slots; see joint_solve_view)
   static LEG_FN W wview(W ws, int group_slots, int X) {
@@ -78,12 +97,14 @@ struct DevDuoB : DevB {
   struct Lds {
     DuoShared* sh;
     int g;
-    double* rec;
-    const double* act;
-    bool has_act, snap;
+    // the group's state record and action row (without actions: the zero row); recl / recm / actl: the same with the lane's leg offset (lo doubles: joints,
+    // ao doubles: motors) folded into the lane offset where the group is selected, so that a slot number is the instruction's immediate offset (added to
+    // `lo` first it is a loop-invariant per-lane value the compiler hoists out of the substep loop and parks, one register per slot)
+    P rec, recl, recm, actl;
+    bool snap;
     int lo, ao;
 #ifdef CASSIE_PHASE_TIMING   // profiling builds (tools/phase_profile.py duo): shader cycles per phase of this wavefront; the time up to mark(k) goes to bucket k
-    unsigned long long t_last, acc[16];
+    unsigned long long t_last, acc[DUO_PHASES];   // 16..21: the pieces of the glue (records in, bookkeeping, outputs, write-back), buckets of their own
     bool rp = false;   // the pass that is running is the reset pass (env_step2)
     LEG_FN void in_reset_pass(bool on) { rp = on; }
     LEG_FN void mark(int k) {
@@ -93,14 +114,17 @@ struct DevDuoB : DevB {
 #ifdef CASSIE_PHASE_RESET_ONLY   // the buckets of the reset pass alone (tools/phase_profile_duo.py); bucket 0 = its glue (with two outputs calls -- terrain -- the second call too)
       if (rp)
 #endif
-      acc[k < 16 ? k : 0] += n - t_last;
+      acc[k < DUO_PHASES ? k : 0] += n - t_last;
       t_last = n;
       __builtin_amdgcn_sched_barrier(0);
     }
 #else
     LEG_FN void mark(int) {}
 #endif
-    template <class IoT> LEG_FN void select(int group, const IoT& io) { g = group; rec = io.rec; act = io.act; has_act = io.has_act; }
+    template <class IoT> LEG_FN void select(int group, const IoT& io) { 
+      g = group; rec = io.rec; recl = io.rec; recm = io.rec; actl = io.act;
+      recl.voff += (unsigned)lo * 8u; recm.voff += (unsigned)ao * 8u; actl.voff += (unsigned)ao * 8u;
+    }
     LEG_FN void snapshot(bool on) { snap = on; }
     // slot of the group's cold block, or -1: not in LDS
     static LEG_FN constexpr int slot(int i) {
@@ -108,20 +132,21 @@ struct DevDuoB : DevB {
     }
     LEG_FN double cld(int i) const {
       const int l = DUO_LANE;
-      if (i < 8) return rec[ES_KQ + (i < 3 ? i : lo + (i - 3))];
-      if (i < 16) return rec[ES_KV + (i - 8 < 3 ? i - 8 : lo + (i - 11))];
-      if (i < 21) return rec[ES_QSTATE + lo + (i - 16)];
-      if (i < 24) return rec[ES_CTRL + ao + (i - 21)];
-      if (i >= 25 && i < 28) return (has_act ? act : duo_zero_action)[ao + (i - 25)];   // (one unconditional load: three of them go out in one batch)
+      if (i < 8) return i < 3 ? pld(rec, ES_KQ + i) : pld(recl, ES_KQ + (i - 3));
+      if (i < 16) return i - 8 < 3 ? pld(rec, ES_KV + (i - 8)) : pld(recl, ES_KV + (i - 11));
+      if (i < 21) return pld(recl, ES_QSTATE + (i - 16));
+      if (i < 24) return pld(recm, ES_CTRL + (i - 21));
+      if (i >= 25 && i < 28) return pld(actl, i - 25);   // (one unconditional load: three of them go out in one batch)
       if (i == 37 || i == 43) return 0.0;   // origin of the pelvis link relative to the pelvis origin
       return sh->cold[g][slot(i)][l];
     }
     LEG_FN void cst(int i, double v, bool m) {
       const int l = DUO_LANE;
       if (i < 16) {
-        if (snap && m) { if (i < 8) rec[ES_KQ + (i < 3 ? i : lo + (i - 3))] = v; else rec[ES_KV + (i - 8 < 3 ? i - 8 : lo + (i - 11))] = v; }
-      } else if (i < 21) { if (m) rec[ES_QSTATE + lo + (i - 16)] = v; }
-      else if (i < 24) { if (m) rec[ES_CTRL + ao + (i - 21)] = v; }
+        const int k = i < 8 ? i : i - 8, f = i < 8 ? ES_KQ : ES_KV;
+        if (k < 3) pst(rec, f + k, v, snap && m); else pst(recl, f + (k - 3), v, snap && m);
+      } else if (i < 21) pst(recl, ES_QSTATE + (i - 16), v, m);
+      else if (i < 24) pst(recm, ES_CTRL + (i - 21), v, m);
       else if (i >= 25 && i < 28) {}
       else if (i == 37 || i == 43) {}
       else { if (m) sh->cold[g][slot(i)][l] = v; }
@@ -155,6 +180,27 @@ struct DevDuoB : DevB {
 typedef Duo<DevDuoB> DDuo;
 static_assert(DDuo::C::C_TIME == 24 && DDuo::C::C_A2 == 28 && DDuo::C::C_TAUB == 29 && DDuo::C::C_OX == 37 && DDuo::C::C_OZ == 43 && DDuo::C::C_N == 49 &&
               DDuo::C::C_KQ == 0 && DDuo::C::C_KV == 8 && DDuo::C::C_QST == 16 && DDuo::C::C_CTRL == 21 && DDuo::C::C_ACT == 25, "DuoLds routes these slot numbers");
+
+// The group's rows of the batch arrays (env_io of cassie_kernels_leg.hip for this backend's P): descriptors over the launch's n_envs rows, lane offsets
+// of environment `env`.  A lane past the batch addresses row 0 (its stores are masked by the caller, as they always were); an array the launch does not
+// have is a descriptor of no bytes; a launch without actions reads the zero row.  32-bit byte offsets: the host keeps a batch whose records exceed 4 GiB out of this tier.
+template <class Io> LEG_FN Io duo_io(const VecParams& p, int env, bool want_obs) {
+  const unsigned n = (unsigned)p.n_envs, e = (unsigned)DevB::opq(env < p.n_envs ? env : 0);
+  auto rows = [](const void* base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);   // (word 3: 32-bit data format, gfx9 encoding)
+  };
+  Io io;
+  io.has_act = p.actions != nullptr;
+  io.has_tobs = p.terminal_obs != nullptr;
+  const unsigned arow = io.has_act ? (unsigned)p.adim * 8u : 0u;
+  io.rec.r = rows(p.state, n * (unsigned)(ENV_STRIDE * 8)); io.rec.voff = e * (unsigned)(ENV_STRIDE * 8);
+  io.act.r = rows(io.has_act ? p.actions : duo_zero_action, io.has_act ? n * arow : (unsigned)sizeof(duo_zero_action)); io.act.voff = e * arow;
+  io.obs.r = rows(p.obs, want_obs ? n * 208u : 0u); io.obs.voff = want_obs ? e * 208u : 0u;
+  io.tobs.r = rows(p.terminal_obs, io.has_tobs ? n * 208u : 0u); io.tobs.voff = io.has_tobs ? e * 208u : 0u;
+  io.rew.r = rows(p.reward, want_obs ? n * 8u : 0u); io.rew.voff = want_obs ? e * 8u : 0u;
+  io.done.r = rows(p.done, want_obs ? n : 0u); io.done.voff = want_obs ? e : 0u;
+  return io;
+}
 
 constexpr size_t duo_workspace_doubles_per_wave = (size_t)DDuo::W_N * 64;
 // THE WORKSPACE IS A PROPERTY OF THE CHIP, NOT OF THE BATCH (r06).  One wavefront of this kernel owns a SIMD (512 registers), so at most
@@ -235,13 +281,13 @@ __global__ void __launch_bounds__(64 * DUO_WAVES, 1) env_step_duo_kernel(VecPara
     valid[g] = env < p.n_envs;
     e[g] = valid[g] ? (size_t)env : 0;
   }
-  // the group's per-lane pointers, rebuilt where a phase needs them (held for the whole kernel they are 24 registers the allocator spills)
+  // the group's descriptors and lane offsets, rebuilt where a phase needs them
   auto io_of = [&](int g) {
     const int env = wave_id * 64 + g * 32 + (lane >> 1);
-    return env_io<DDuo::Io>(p, env < p.n_envs ? (size_t)env : 0, cfg.want_obs);
+    return duo_io<DDuo::Io>(p, env, cfg.want_obs);
   };
   DevDuoB::Lds lds;
-  lds.sh = &sh; lds.g = 0; lds.rec = p.state; lds.act = p.actions; lds.has_act = false; lds.snap = true;
+  lds.sh = &sh; lds.g = 0; lds.snap = true;   // (rec / act: Lds::select, before any access)
   lds.lo = (lane & 1) * 5 + 3; lds.ao = (lane & 1) * 3;
   DDuo::Out o[2];
   DevDuoB::W ws;   // raw buffer over this wavefront's W_N x 512 bytes (word 3: 32-bit data format, gfx9 encoding)
@@ -249,14 +295,14 @@ __global__ void __launch_bounds__(64 * DUO_WAVES, 1) env_step_duo_kernel(VecPara
   ws.r = __builtin_amdgcn_make_buffer_rsrc(workspace + (size_t)slot * duo_workspace_doubles_per_wave, 0, DDuo::W_N * 512, 0x00020000);
   ws.voff = (unsigned)lane * 16u;
 #ifdef CASSIE_PHASE_TIMING
-  for (int i = 0; i < 16; i++) lds.acc[i] = 0;
+  for (int i = 0; i < DUO_PHASES; i++) lds.acc[i] = 0;
   lds.t_last = __builtin_readcyclecounter();
 #endif
   DDuo::env_step2<MODE>(cfg, lds, ws, io_of, valid, o);
   sl.release(lane, slot);   // (the write-back at the end of env_step2 has consumed its loads from the workspace: they fed its stores to the records)
 #ifdef CASSIE_PHASE_TIMING
   lds.mark(0);
-  if (lane == 0 && p.phase) for (int i = 0; i < 16; i++) atomicAdd(p.phase + i, lds.acc[i]);
+  if (lane == 0 && p.phase) for (int i = 0; i < DUO_PHASES; i++) atomicAdd(p.phase + i, lds.acc[i]);
 #endif
 #pragma unroll
   for (int g = 0; g < 2; g++)
@@ -321,10 +367,10 @@ __global__ void __launch_bounds__(64 * DUO_WAVES, 1) env_step_duo_hf_kernel(VecP
   }
   auto io_of = [&](int g) {
     const int env = wave_id * 64 + g * 32 + (lane >> 1);
-    return env_io<DDuoHF::Io>(p, env < p.n_envs ? (size_t)env : 0, cfg.want_obs);
+    return duo_io<DDuoHF::Io>(p, env, cfg.want_obs);
   };
   DevDuoBHF::Lds lds;
-  lds.sh = &sh; lds.shf = &sh; lds.g = 0; lds.rec = p.state; lds.act = p.actions; lds.has_act = false; lds.snap = true;
+  lds.sh = &sh; lds.shf = &sh; lds.g = 0; lds.snap = true;   // (rec / act: Lds::select, before any access)
   lds.lo = (lane & 1) * 5 + 3; lds.ao = (lane & 1) * 3;
   lds.a2[0] = 0.0; lds.a2[1] = 0.0;
   {

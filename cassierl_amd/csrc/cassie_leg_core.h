@@ -1212,14 +1212,19 @@ template <class B> struct Core {
     D ob[5], of[6];
     ob[0] = zz; ob[1] = pitch; ob[2] = body[2]; ob[3] = body[3]; ob[4] = st.vb[2];
     of[0] = foot[0] - bodyx; of[1] = foot[1]; of[2] = 0.0; of[3] = foot[2]; of[4] = foot[3]; of[5] = 0.0;
-    auto put = [&](typename B::P row, M m) {
-      lfor<0, 5>([&](auto ii) { constexpr int Ii = decltype(ii)::value; B::pst(row, I(Ii), ob[Ii], m & left); });
-      lfor<0, 6>([&](auto ii) { constexpr int Ii = decltype(ii)::value; B::pst(row, leg * 6 + (5 + Ii), of[Ii], m); });
-    };
+    // An observation row goes out mask by mask -- the five body values (left lane), the lane's own foot (both lanes), the nine trajectory slots (right
+    // lane) -- and every caller below issues its stores grouped by mask: consecutive stores under one mask are one region of the lanes' execution mask,
+    // and no load stands behind a store (a load behind a store waits for every store before it: cassie_kernels_duo.hip).
+    auto put_body = [&](typename B::P row, const D (&b)[5], M m) { lfor<0, 5>([&](auto ii) { constexpr int Ii = decltype(ii)::value; B::pst(row, I(Ii), b[Ii], m); }); };
+    auto put_foot = [&](typename B::P row, const D (&f)[6], M m) { lfor<0, 6>([&](auto ii) { constexpr int Ii = decltype(ii)::value; B::pst(row, leg * 6 + (5 + Ii), f[Ii], m); }); };
+    auto put_traj = [&](typename B::P row, const D (&r)[9], M m) { lfor<0, 9>([&](auto ii) { constexpr int Ii = decltype(ii)::value; B::pst(row, I(17 + Ii), r[Ii], m); }); };
     if (reset_pass) {
       // Cassie2dEnv.reset returns the 17 op-space values; the trajectory slots of the observation are zero there
-      put(io.obs, o.do_reset);
-      lfor<0, 9>([&](auto ii) { constexpr int Ii = decltype(ii)::value; B::pst(io.obs, I(17 + Ii), D(0.0), o.do_reset & !left); });
+      D zero[9];
+      lfor<0, 9>([&](auto ii) { constexpr int Ii = decltype(ii)::value; zero[Ii] = 0.0; });
+      put_body(io.obs, ob, o.do_reset & left);
+      put_foot(io.obs, of, o.do_reset);
+      put_traj(io.obs, zero, o.do_reset & !left);
       return false;
     }
     D ref[9];
@@ -1272,59 +1277,72 @@ template <class B> struct Core {
     lfor<0, 9>([&](auto ii) { constexpr int Ii = decltype(ii)::value; ref[Ii] = B::sel(bad, D(0.0), ref[Ii]); });
     reward = B::sel(bad, D(0.0), reward);
     done = done | bad;
-    if (cfg.auto_reset) {
-      // the reset below also clears every NaN carrier (warm start, ctrl, setState copies)
+    const bool clear_bad = cfg.auto_reset != 0;   // the reset below also clears every NaN carrier (warm start, ctrl, setState copies)
+    if (clear_bad) {
+      lfor<0, 3>([&](auto bb) { constexpr int Bc = decltype(bb)::value; st.wb[Bc] = B::sel(bad, D(0.0), st.wb[Bc]); });
+      lfor<0, 5>([&](auto dd) { constexpr int Dd = decltype(dd)::value; st.wl[Dd] = B::sel(bad, D(0.0), st.wl[Dd]); });
+      o.set_state = o.set_state | bad;
+    }
+    o.do_reset = live & done & (cfg.auto_reset != 0);
+    const bool resets = B::any(o.do_reset);
+    // ---- everything that is stored is computed first.  The row of io.obs (rowb / rowf / rowt): the step's observation; with ONE_SECTION the reset
+    // observation on the lanes of do_reset -- ONE write of the row, where the two-call form writes the step's row and then the reset row over it.
+    D rowb[5], rowf[6], rowt[9];
+    lfor<0, 5>([&](auto ii) { constexpr int Ii = decltype(ii)::value; rowb[Ii] = ob[Ii]; });
+    lfor<0, 6>([&](auto ii) { constexpr int Ii = decltype(ii)::value; rowf[Ii] = of[Ii]; });
+    lfor<0, 9>([&](auto ii) { constexpr int Ii = decltype(ii)::value; rowt[Ii] = ref[Ii]; });
+    D qi[5];
+    lfor<0, 5>([&](auto dd) { constexpr int Dd = decltype(dd)::value; qi[Dd] = ldc(cp_env_qinit, lo + Dd); });
+    if (resets) {
+      // ---- Cassie2dEnv.reset for the terminated environments: qinit, mj_forward with the stale ctrl, no setState
+      lfor<0, 3>([&](auto bb) { constexpr int Bc = decltype(bb)::value; st.qb[Bc] = B::sel(o.do_reset, D(cp_env_qinit[Bc]), st.qb[Bc]); st.vb[Bc] = B::sel(o.do_reset, D(0.0), st.vb[Bc]); });
+      lfor<0, 5>([&](auto dd) { constexpr int Dd = decltype(dd)::value; st.ql[Dd] = B::sel(o.do_reset, qi[Dd], st.ql[Dd]); st.vl[Dd] = B::sel(o.do_reset, D(0.0), st.vl[Dd]); });
+      if constexpr (ONE_SECTION) {
+        // The reset observation (what the second call stores): the 17 operational-space values of the LAST setState with the pitch and pitch rate of
+        // the reset pose, trajectory slots zero.  The reset pass does no setState, so the snapshot the second call reads is the one this call has just
+        // used -- ob / of above are its values -- except where this call re-writes it (failure guard: the reset pose at rest) or does not read it
+        // (FLAG_FIX_STALE_KIN: the state, by then the reset pose at rest).  Those lanes (`own`) take the operational-space state of `st`, which holds
+        // the reset pose at rest on every lane of do_reset from here on.
+        const M rs = o.do_reset;
+        const M own = fix_kin ? rs : (rs & bad);
+        D rb[5], rf[6];
+        lfor<0, 5>([&](auto ii) { constexpr int Ii = decltype(ii)::value; rb[Ii] = ob[Ii]; });
+        lfor<0, 6>([&](auto ii) { constexpr int Ii = decltype(ii)::value; rf[Ii] = of[Ii]; });
+        if (B::any(own)) {
+          D body1[4], foot1[4];
+          opstate(st.qb, st.ql, st.vb, st.vl, body1, foot1);
+          rb[0] = B::sel(own, body1[1], rb[0]); rb[2] = B::sel(own, body1[2], rb[2]); rb[3] = B::sel(own, body1[3], rb[3]);
+          rf[0] = B::sel(own, foot1[0] - body1[0], rf[0]); rf[1] = B::sel(own, foot1[1], rf[1]); rf[3] = B::sel(own, foot1[2], rf[3]); rf[4] = B::sel(own, foot1[3], rf[4]);
+        }
+        rb[1] = st.qb[2]; rb[4] = st.vb[2];
+        lfor<0, 5>([&](auto ii) { constexpr int Ii = decltype(ii)::value; rowb[Ii] = B::sel(rs, rb[Ii], ob[Ii]); });
+        lfor<0, 6>([&](auto ii) { constexpr int Ii = decltype(ii)::value; rowf[Ii] = B::sel(rs, rf[Ii], of[Ii]); });
+        lfor<0, 9>([&](auto ii) { constexpr int Ii = decltype(ii)::value; rowt[Ii] = B::sel(rs, D(0.0), ref[Ii]); });
+      }
+    }
+    // ---- the stores, mask by mask: live & left, live, live & !left, then the record slots of the failure guard (bad) and of the reset (do_reset)
+    {
+      const M ll = live & left, lr = live & !left;
+      if (io.has_tobs) put_body(io.tobs, ob, ll);
+      put_body(io.obs, rowb, ll);
+      B::pst(io.rew, I(0), reward, ll);
+      B::pst8(io.done, done, ll);
+      if (io.has_tobs) put_foot(io.tobs, of, live);
+      put_foot(io.obs, rowf, live);
+      if (io.has_tobs) put_traj(io.tobs, ref, lr);
+      put_traj(io.obs, rowt, lr);
+    }
+    if (clear_bad) {
       lfor<0, 3>([&](auto bb) {
         constexpr int Bc = decltype(bb)::value;
-        st.wb[Bc] = B::sel(bad, D(0.0), st.wb[Bc]);
         lds.cst(C_KQ + Bc, D(cp_env_qinit[Bc]), bad); lds.cst(C_KV + Bc, D(0.0), bad);
         lds.cst(C_CTRL + Bc, D(0.0), bad);
       });
-      lfor<0, 5>([&](auto dd) {
-        constexpr int Dd = decltype(dd)::value;
-        st.wl[Dd] = B::sel(bad, D(0.0), st.wl[Dd]);
-        lds.cst(C_KQ + 3 + Dd, ldc(cp_env_qinit, lo + Dd), bad); lds.cst(C_KV + 3 + Dd, D(0.0), bad);
-      });
-      o.set_state = o.set_state | bad;
+      lfor<0, 5>([&](auto dd) { constexpr int Dd = decltype(dd)::value; lds.cst(C_KQ + 3 + Dd, qi[Dd], bad); lds.cst(C_KV + 3 + Dd, D(0.0), bad); });
     }
-    if (io.has_tobs) {
-      put(io.tobs, live);
-      lfor<0, 9>([&](auto ii) { constexpr int Ii = decltype(ii)::value; B::pst(io.tobs, I(17 + Ii), ref[Ii], live & !left); });
-    }
-    put(io.obs, live);
-    lfor<0, 9>([&](auto ii) { constexpr int Ii = decltype(ii)::value; B::pst(io.obs, I(17 + Ii), ref[Ii], live & !left); });
-    B::pst(io.rew, I(0), reward, live & left);
-    B::pst8(io.done, done, live & left);
-    o.do_reset = live & done & (cfg.auto_reset != 0);
-    if (!B::any(o.do_reset)) return false;
-    // ---- Cassie2dEnv.reset for the terminated environments: qinit, mj_forward with the stale ctrl, no setState
-    lfor<0, 3>([&](auto bb) { constexpr int Bc = decltype(bb)::value; st.qb[Bc] = B::sel(o.do_reset, D(cp_env_qinit[Bc]), st.qb[Bc]); st.vb[Bc] = B::sel(o.do_reset, D(0.0), st.vb[Bc]); });
-    lfor<0, 5>([&](auto dd) {
-      constexpr int Dd = decltype(dd)::value;
-      const D qi = ldc(cp_env_qinit, lo + Dd);
-      st.ql[Dd] = B::sel(o.do_reset, qi, st.ql[Dd]); st.vl[Dd] = B::sel(o.do_reset, D(0.0), st.vl[Dd]);
-      lds.cst(C_QST + Dd, qi, o.do_reset);
-    });
+    if (!resets) return false;
+    lfor<0, 5>([&](auto dd) { constexpr int Dd = decltype(dd)::value; lds.cst(C_QST + Dd, qi[Dd], o.do_reset); });
     lds.cst(C_TIME, D(0.0), o.do_reset);
-    if constexpr (ONE_SECTION) {
-      // The reset observation (what the second call stores): the 17 operational-space values of the LAST setState with the pitch and pitch rate of
-      // the reset pose, trajectory slots zero.  The reset pass does no setState, so the snapshot the second call reads is the one this call has just
-      // used -- ob / of above are its values -- except where this call re-wrote it (failure guard: the reset pose at rest) or does not read it
-      // (FLAG_FIX_STALE_KIN: the state, by then the reset pose at rest).  Those lanes (`own`) take the operational-space state of `st`, which holds
-      // the reset pose at rest on every lane of do_reset from here on.
-      // The row just stored is overwritten for the lanes of do_reset (same lane, same address, program order).
-      const M rs = o.do_reset;
-      const M own = fix_kin ? rs : (rs & bad);
-      if (B::any(own)) {
-        D body1[4], foot1[4];
-        opstate(st.qb, st.ql, st.vb, st.vl, body1, foot1);
-        ob[0] = B::sel(own, body1[1], ob[0]); ob[2] = B::sel(own, body1[2], ob[2]); ob[3] = B::sel(own, body1[3], ob[3]);
-        of[0] = B::sel(own, foot1[0] - body1[0], of[0]); of[1] = B::sel(own, foot1[1], of[1]); of[3] = B::sel(own, foot1[2], of[3]); of[4] = B::sel(own, foot1[3], of[4]);
-      }
-      ob[1] = st.qb[2]; ob[4] = st.vb[2];
-      put(io.obs, rs);
-      lfor<0, 9>([&](auto ii) { constexpr int Ii = decltype(ii)::value; B::pst(io.obs, I(17 + Ii), D(0.0), rs & !left); });
-    }
     return true;   // the reset pose on the flat floor has 12 rows: never an overflow
   }
 

@@ -26,7 +26,7 @@ if len(sys.argv) > 3 and sys.argv[3] == "physics":
         out = env.alloc()
         env.reset(out)
         ids = torch.arange(n, device="cuda")
-        buf = (ct.c_ulonglong * 16)()
+        buf = (ct.c_ulonglong * 24)()
         env.L.CassieVecPhaseCycles.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
         for t in range(10):
             env.step(R.random_actions(1, ids, t, env.action_space.low, env.action_space.high), out)
@@ -57,7 +57,7 @@ ids = torch.arange(n, device="cuda")
 lo, hi = np.array([-2, -2, -2, 0, -2, 0, -2.0]), np.full(7, 2.0)
 zp = torch.full((n,), 0.9, dtype=torch.float64, device="cuda")
 zv = torch.zeros(n, dtype=torch.float64, device="cuda")
-buf = (ct.c_ulonglong * 16)()
+buf = (ct.c_ulonglong * 24)()
 env.L.CassieVecPhaseCycles.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
 for rep in range(2):
     for t in range(10):

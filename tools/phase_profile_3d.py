@@ -18,7 +18,7 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 env = Cassie3dVec(n)
 ids = torch.arange(n, device="cuda")
 acts = [R.random_actions(5, ids, t, -CTRL_RANGE, CTRL_RANGE) for t in range(60)]
-buf = (ct.c_ulonglong * 16)()
+buf = (ct.c_ulonglong * 24)()
 f = env.L.Cassie3dDebugPhaseCycles
 f.argtypes = [ct.POINTER(ct.c_ulonglong)]
 for t in range(30):
