@@ -21,6 +21,9 @@
 //     so that the single-workgroup apply kernel reads 2 MB and not 18.
 // Every sum runs in a fixed order (k-ordered MFMA chains, tiles in a fixed order per wavefront, a fixed grid for a given n): a run repeats
 // bit for bit.
+// The building blocks are mlp32_tiles.h's, shared with tu_sac.hip and tu_td3.hip: the gather of a tile, the forward passes, the live critic's tile
+// pass, the actor's reverse pass, the row stores, the policy step's body and the Adam step.  This unit keeps the target of its critic kernel, the
+// cotangent of its actor kernel, the Ornstein-Uhlenbeck head of its policy step, the pool commit and the entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -31,12 +34,12 @@
 
 namespace cassie_ddpg {
 
-using namespace cassie_mlp32;   // shapes, operand images, tile helpers (shared with tu_sac.hip)
+using namespace cassie_mlp32;   // shapes, operand images, tile helpers (shared with tu_sac.hip, tu_td3.hip)
 
 // ---------------------------------------------------------------------------------------------------------------- critic gradient
 // Per sample b of the batch (pool row i = idx[b]):  y = r_i + (1 - terminal_i) gamma Q'(s'_i, mu'(s'_i)),  e = Q(s_i, a_i) - y, and the
 // gradient of sum_b e^2 with respect to the live critic.  Row: [gW1 | gb1 | gW2 | gb2 | gW3 | gb3 | sum e^2 | sum Q].
-enum { CQ_TA_W1 = 0, CQ_TA_W2 = 4, CQ_TA_W3 = 8, CQ_TQ_W1 = 12, CQ_TQ_W2 = 16, CQ_TQ_A = 20, CQ_Q_W1 = 21, CQ_Q_W2 = 25, CQ_Q_A = 29, CQ_Q_W2T = 30, CQ_N = 34 };
+enum { CQ_TA = 0, CQ_TQ = LA_N, CQ_Q = CQ_TQ + LQ_FWD, CQ_N = CQ_Q + LQ_N };
 template <int D, int A>
 __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, const long long* __restrict__ idx, int n, Net ta, Net tq, Net q, float gamma,
                                                                     float* __restrict__ partial) {
@@ -45,138 +48,55 @@ __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, c
   constexpr int KS1 = (D + 1) / 2, NROW = S::NPQ + 2;
   static_assert(WAVES * NROW <= WAVES * 2 * 32 * TP, "the workgroup's reduction re-uses the transpose tiles");
   __shared__ alignas(16) float tilemem[WAVES * 2 * 32 * TP];
-  __shared__ alignas(16) float sbias[7][32];   // target actor b1 b2 b3, target critic b1 b2, live critic b1 b2
+  __shared__ alignas(16) float sbias[8][32];   // target actor b1 b2 b3;  target critic b1 b2 (its W3 in registers);  live critic b1 b2 W3
   __shared__ float4 wimg[CQ_N][64];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, h = lane >> 5;
   if (tid < 32) {
-    sbias[0][tid] = ta.b1[tid]; sbias[1][tid] = ta.b2[tid]; sbias[2][tid] = tid < A ? ta.b3[tid] : 0.0f;
-    sbias[3][tid] = tq.b1[tid]; sbias[4][tid] = tq.b2[tid]; sbias[5][tid] = q.b1[tid]; sbias[6][tid] = q.b2[tid];
+    sbias[0][tid] = ta.b1[tid]; sbias[1][tid] = ta.b2[tid]; sbias[2][tid] = out_bias<A, K_OUT>(ta.b3, tid);
+    sbias[3][tid] = tq.b1[tid]; sbias[4][tid] = tq.b2[tid];
+    sbias[5][tid] = q.b1[tid]; sbias[6][tid] = q.b2[tid]; sbias[7][tid] = q.W3[tid];
   }
   {
-    const Grp g[10] = {{K_FIRST, ta.W1, CQ_TA_W1, 4}, {K_HID, ta.W2, CQ_TA_W2, 4}, {K_OUT, ta.W3, CQ_TA_W3, 4}, {K_FIRST, tq.W1, CQ_TQ_W1, 4},
-                       {K_HIDQ, tq.W2, CQ_TQ_W2, 4}, {K_ACTIN, tq.W2, CQ_TQ_A, 1}, {K_FIRST, q.W1, CQ_Q_W1, 4}, {K_HIDQ, q.W2, CQ_Q_W2, 4},
-                       {K_ACTIN, q.W2, CQ_Q_A, 1}, {K_HIDQT, q.W2, CQ_Q_W2T, 4}};
+    const Grp g[10] = {{K_FIRST, ta.W1, CQ_TA + LA_W1, 4}, {K_HID, ta.W2, CQ_TA + LA_W2, 4}, {K_OUT, ta.W3, CQ_TA + LA_W3, 4},
+                       {K_FIRST, tq.W1, CQ_TQ + LQ_W1, 4}, {K_HIDQ, tq.W2, CQ_TQ + LQ_W2, 4}, {K_ACTIN, tq.W2, CQ_TQ + LQ_A, 1},
+                       {K_FIRST, q.W1, CQ_Q + LQ_W1, 4}, {K_HIDQ, q.W2, CQ_Q + LQ_W2, 4}, {K_ACTIN, q.W2, CQ_Q + LQ_A, 1}, {K_HIDQT, q.W2, CQ_Q + LQ_W2T, 4}};
     fill_images<D, A>(wimg, g, wave, lane);
   }
-  float w3t[16], w3q[16];
+  float w3t[16];   // in registers: read from a row of sbias like the live critic's, the kernel takes 228 + 52 registers, not 186 + 48, and occupancy 1
 #pragma unroll
-  for (int v = 0; v < 16; v++) { w3t[v] = tq.W3[row_of(v, h)]; w3q[v] = q.W3[row_of(v, h)]; }
+  for (int v = 0; v < 16; v++) w3t[v] = tq.W3[row_of(v, h)];
   const float b3t = tq.b3[0], b3q = q.b3[0];
   __syncthreads();
   float* t0 = tilemem + (wave * 2) * 32 * TP;
   float* t1 = t0 + 32 * TP;
-  v16f gW1, gW2, gW2a;
-  float gW3[16];
-#pragma unroll
-  for (int v = 0; v < 16; v++) { gW1[v] = 0.0f; gW2[v] = 0.0f; gW2a[v] = 0.0f; gW3[v] = 0.0f; }
-  float gb2 = 0.0f, gb3 = 0.0f, sse = 0.0f, sq = 0.0f;
+  CriticAcc acc;
+  zero(acc);
   const int ntiles = (n + 31) / 32;
   for (int tl = blockIdx.x * WAVES + wave; tl < ntiles; tl += gridDim.x * WAVES) {
-    const int s0 = tl * 32, smp = s0 + c;
-    const bool valid = smp < n;
-    const long long gi = valid ? clamp_row(idx[smp], pool.cap) : 0;
-    float xb[KS1], xn[KS1], ab[4], xt[16], at[16];
-#pragma unroll
-    for (int s = 0; s < KS1; s++) {
-      const int k = 2 * s + h;
-      const bool on = valid && k < D;
-      xb[s] = on ? pool.obs[gi * D + k] : 0.0f; xn[s] = on ? pool.nobs[gi * D + k] : 0.0f;
-    }
-#pragma unroll
-    for (int v = 0; v < 4; v++) ab[v] = (valid && v + 4 * h < A) ? pool.act[gi * A + v + 4 * h] : 0.0f;
-    // transposed operands of the parameter gradients: feature (action component) on the lane, column D (A) = ones
-#pragma unroll
-    for (int s = 0; s < 16; s++) {
-      const int sm = s0 + 16 * h + s;
-      const bool on = sm < n;
-      const long long gs = on ? clamp_row(idx[sm], pool.cap) : 0;
-      xt[s] = c < D ? (on ? pool.obs[gs * D + c] : 0.0f) : (c == D ? 1.0f : 0.0f);
-      at[s] = (c < A && on) ? pool.act[gs * A + c] : 0.0f;
-    }
-    const float rew = valid ? pool.rew[gi] : 0.0f, live = valid ? 1.0f - pool.term[gi] : 0.0f;
+    Tile<D, A> t;
+    gather<true>(pool, idx, n, tl, c, h, t);
     // ---- target: Q'(s', mu'(s'))
-    v16f u1, u2;
-    float mt[4];
+    float y;
     {
-      v16f a1, a2;
-      two_layers<KS1>(wimg, CQ_TA_W1, CQ_TA_W2, sbias[0], sbias[1], xn, lane, h, a1, a2);
-      relu16(a2);
-      float aw[16];
-      v16f mu = bias_tile(sbias[2], h);
-      aop(wimg, CQ_TA_W3, lane, aw);
-#pragma unroll
-      for (int v = 0; v < 16; v++) mu = TILE_MFMA(aw[v], a2[v], mu);
+      v16f a1, a2, mu, u1, u2;
+      float mt[4];
+      actor_forward<KS1>(wimg, CQ_TA, sbias, t.xn, lane, h, a1, a2, mu);
 #pragma unroll
       for (int v = 0; v < 4; v++) mt[v] = tanh_fast(mu[v]);   // rows a >= A: W3 and b3 padded with zeros -> tanh(0) = 0
+      y = t.rew + t.live * gamma * critic_forward<KS1>(wimg, CQ_TQ, sbias + 3, w3t, b3t, t.xn, mt, lane, h, u1, u2);
     }
-    two_layers<KS1>(wimg, CQ_TQ_W1, CQ_TQ_W2, sbias[3], sbias[4], xn, lane, h, u1, u2);
-    add_action(wimg, CQ_TQ_A, lane, mt, u2);
-    relu16(u2);
-    const float y = rew + live * gamma * q_head(w3t, b3t, u2);
-    // ---- live critic at (s, a)
-    v16f c1, c2;
-    two_layers<KS1>(wimg, CQ_Q_W1, CQ_Q_W2, sbias[5], sbias[6], xb, lane, h, c1, c2);
-    add_action(wimg, CQ_Q_A, lane, ab, c2);
-    relu16(c2);
-    const float qv = q_head(w3q, b3q, c2);
-    const float e = valid ? qv - y : 0.0f, dq = 2.0f * e;
-    if (h == 0 && valid) { sse += e * e; sq += qv; gb3 += dq; }
-    // ---- reverse mode: G2 = (W3' dq) o (h2 > 0), G1 = (W2h' G2) o (h1 > 0)
-    v16f g2, g1;
-#pragma unroll
-    for (int v = 0; v < 16; v++) {
-      gW3[v] = __builtin_fmaf(dq, c2[v], gW3[v]);
-      g2[v] = c2[v] > 0.0f ? w3q[v] * dq : 0.0f;
-      g1[v] = 0.0f;
-    }
-    float aw[16], ta_[16], tb_[16];
-    aop(wimg, CQ_Q_W2T, lane, aw);
-#pragma unroll
-    for (int v = 0; v < 16; v++) g1 = TILE_MFMA(aw[v], g2[v], g1);
-#pragma unroll
-    for (int v = 0; v < 16; v++) g1[v] = c1[v] > 0.0f ? g1[v] : 0.0f;
-    put(t0, g2, c, h); put(t1, c1, c, h);
-    wave_lds_sync();
-    get(t0, ta_, c, h); get(t1, tb_, c, h);
-    wave_lds_sync();
-#pragma unroll
-    for (int s = 0; s < 16; s++) { gW2 = TILE_MFMA(ta_[s], tb_[s], gW2); gW2a = TILE_MFMA(ta_[s], at[s], gW2a); gb2 += ta_[s]; }
-    put(t0, g1, c, h);
-    wave_lds_sync();
-    get(t0, ta_, c, h);
-    wave_lds_sync();
-#pragma unroll
-    for (int s = 0; s < 16; s++) gW1 = TILE_MFMA(ta_[s], xt[s], gW1);
+    critic_step(wimg, CQ_Q, sbias + 5, b3q, t, y, lane, c, h, t0, t1, acc);   // the live critic at (s, a)
   }
   // ---- this wavefront's row in LDS (the tiles are free once every wavefront has left the loop), then one row per workgroup
-#pragma unroll
-  for (int v = 0; v < 16; v++) {
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) gW3[v] += __shfl_xor(gW3[v], m, 64);   // over the 32 samples of the lane half
-  }
-#pragma unroll
-  for (int m = 16; m >= 1; m >>= 1) { sse += __shfl_xor(sse, m, 64); sq += __shfl_xor(sq, m, 64); gb3 += __shfl_xor(gb3, m, 64); }
-  gb2 += __shfl_xor(gb2, 32, 64);
   __syncthreads();
-  float* red = tilemem + wave * NROW;
-#pragma unroll
-  for (int v = 0; v < 16; v++) {
-    const int r = row_of(v, h);
-    red[S::Q_W2 + r * S::HA + c] = gW2[v];
-    if (c < A) red[S::Q_W2 + r * S::HA + H + c] = gW2a[v];
-    if (c < D) red[S::Q_W1 + r * D + c] = gW1[v];
-    if (c == D) red[S::Q_B1 + r] = gW1[v];
-    if (c == 0) red[S::Q_W3 + r] = gW3[v];
-  }
-  if (h == 0) red[S::Q_B2 + c] = gb2;
-  if (lane == 0) { red[S::Q_B3] = gb3; red[S::NPQ] = sse; red[S::NPQ + 1] = sq; }
+  critic_row<D, A>(acc, tilemem + wave * NROW, lane, c, h);
   __syncthreads();
   reduce_rows<NROW>(tilemem, partial + (size_t)blockIdx.x * NROW);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- actor gradient
 // Gradient of -sum_b Q(s_b, mu(s_b)) with respect to the actor, through the live critic.  Row: [gW1 | gb1 | gW2 | gb2 | gW3 | gb3 | sum Q].
-enum { AG_W1 = 0, AG_W2 = 4, AG_W3 = 8, AG_W2T = 12, AG_W3T = 16, AG_Q_W1 = 17, AG_Q_W2 = 21, AG_Q_A = 25, AG_Q_DA = 26, AG_N = 30 };
+enum { AG_PI = 0, AG_W2T = LA_N, AG_W3T = 16, AG_Q = 17, AG_Q_DA = AG_Q + LQ_FWD, AG_N = AG_Q_DA + 4 };
 template <int D, int A>
 __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, const long long* __restrict__ idx, int n, Net th, Net q, float* __restrict__ partial) {
   typedef Shape<D, A> S;
@@ -184,16 +104,17 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
   constexpr int KS1 = (D + 1) / 2, NROW = S::NPA + 1;
   static_assert(WAVES * NROW <= WAVES * 2 * 32 * TP, "the workgroup's reduction re-uses the transpose tiles");
   __shared__ alignas(16) float tilemem[WAVES * 2 * 32 * TP];
-  __shared__ alignas(16) float sbias[5][32];   // actor b1 b2 b3, critic b1 b2
+  __shared__ alignas(16) float sbias[5][32];   // actor b1 b2 b3, critic b1 b2 (its W3 stays in registers: the LDS of this kernel is full)
   __shared__ float4 wimg[AG_N][64];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, h = lane >> 5;
   if (tid < 32) {
-    sbias[0][tid] = th.b1[tid]; sbias[1][tid] = th.b2[tid]; sbias[2][tid] = tid < A ? th.b3[tid] : 0.0f;
+    sbias[0][tid] = th.b1[tid]; sbias[1][tid] = th.b2[tid]; sbias[2][tid] = out_bias<A, K_OUT>(th.b3, tid);
     sbias[3][tid] = q.b1[tid]; sbias[4][tid] = q.b2[tid];
   }
   {
-    const Grp g[9] = {{K_FIRST, th.W1, AG_W1, 4}, {K_HID, th.W2, AG_W2, 4}, {K_OUT, th.W3, AG_W3, 4}, {K_HIDT, th.W2, AG_W2T, 4}, {K_W3T, th.W3, AG_W3T, 1},
-                      {K_FIRST, q.W1, AG_Q_W1, 4}, {K_HIDQ, q.W2, AG_Q_W2, 4}, {K_ACTIN, q.W2, AG_Q_A, 1}, {K_DA, q.W2, AG_Q_DA, 4}};
+    const Grp g[9] = {{K_FIRST, th.W1, AG_PI + LA_W1, 4}, {K_HID, th.W2, AG_PI + LA_W2, 4}, {K_OUT, th.W3, AG_PI + LA_W3, 4}, {K_HIDT, th.W2, AG_W2T, 4},
+                      {K_W3T, th.W3, AG_W3T, 1}, {K_FIRST, q.W1, AG_Q + LQ_W1, 4}, {K_HIDQ, q.W2, AG_Q + LQ_W2, 4}, {K_ACTIN, q.W2, AG_Q + LQ_A, 1},
+                      {K_DA, q.W2, AG_Q_DA, 4}};
     fill_images<D, A>(wimg, g, wave, lane);
   }
   float w3q[16];
@@ -203,45 +124,23 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
   __syncthreads();
   float* t0 = tilemem + (wave * 2) * 32 * TP;
   float* t1 = t0 + 32 * TP;
-  v16f gW1, gW2, gW3;
-#pragma unroll
-  for (int v = 0; v < 16; v++) { gW1[v] = 0.0f; gW2[v] = 0.0f; gW3[v] = 0.0f; }
-  float gb2 = 0.0f, gb3 = 0.0f, sq = 0.0f;
+  ActorAcc acc;
+  zero(acc);
+  float sq = 0.0f;
   const int ntiles = (n + 31) / 32;
   for (int tl = blockIdx.x * WAVES + wave; tl < ntiles; tl += gridDim.x * WAVES) {
-    const int s0 = tl * 32, smp = s0 + c;
-    const bool valid = smp < n;
-    const long long gi = valid ? clamp_row(idx[smp], pool.cap) : 0;
-    float xb[KS1], xt[16];
-#pragma unroll
-    for (int s = 0; s < KS1; s++) { const int k = 2 * s + h; xb[s] = (valid && k < D) ? pool.obs[gi * D + k] : 0.0f; }
-#pragma unroll
-    for (int s = 0; s < 16; s++) {
-      const int sm = s0 + 16 * h + s;
-      const bool on = sm < n;
-      const long long gs = on ? clamp_row(idx[sm], pool.cap) : 0;
-      xt[s] = c < D ? (on ? pool.obs[gs * D + c] : 0.0f) : (c == D ? 1.0f : 0.0f);
-    }
+    Tile<D, A> t;
+    gather<false>(pool, idx, n, tl, c, h, t);
     // ---- actor forward: mu(s), action a = v + 4 h in register v < 4
-    v16f a1, a2;
+    v16f a1, a2, z3;
     float aw[16], mu[4];
-    two_layers<KS1>(wimg, AG_W1, AG_W2, sbias[0], sbias[1], xb, lane, h, a1, a2);
-    relu16(a2);
-    {
-      v16f z3 = bias_tile(sbias[2], h);
-      aop(wimg, AG_W3, lane, aw);
+    actor_forward<KS1>(wimg, AG_PI, sbias, t.xb, lane, h, a1, a2, z3);
 #pragma unroll
-      for (int v = 0; v < 16; v++) z3 = TILE_MFMA(aw[v], a2[v], z3);
-#pragma unroll
-      for (int v = 0; v < 4; v++) mu[v] = tanh_fast(z3[v]);
-    }
+    for (int v = 0; v < 4; v++) mu[v] = tanh_fast(z3[v]);
     // ---- critic at (s, mu(s)) and dQ/da = W2a' (W3 o (h2 > 0))
     v16f c1, c2, da;
-    two_layers<KS1>(wimg, AG_Q_W1, AG_Q_W2, sbias[3], sbias[4], xb, lane, h, c1, c2);
-    add_action(wimg, AG_Q_A, lane, mu, c2);
-    relu16(c2);
-    const float qv = q_head(w3q, b3q, c2);
-    if (h == 0 && valid) sq += qv;
+    const float qv = critic_forward<KS1>(wimg, AG_Q, sbias + 3, w3q, b3q, t.xb, mu, lane, h, c1, c2);
+    if (h == 0 && t.valid) sq += qv;
 #pragma unroll
     for (int v = 0; v < 16; v++) da[v] = 0.0f;
     aop(wimg, AG_Q_DA, lane, aw);
@@ -252,133 +151,42 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
 #pragma unroll
     for (int v = 0; v < 16; v++) wt[v] = 0.0f;
 #pragma unroll
-    for (int v = 0; v < 4; v++) wt[v] = (valid && v + 4 * h < A) ? -da[v] * (1.0f - mu[v] * mu[v]) : 0.0f;
-    // ---- the actor's reverse pass (tu_trpo.hip with the ReLU mask)
-    v16f g2, g1;
-#pragma unroll
-    for (int v = 0; v < 16; v++) { g2[v] = 0.0f; g1[v] = 0.0f; }
-    {
-      const float4 w = wimg[AG_W3T][lane];
-      g2 = TILE_MFMA(w.x, wt[0], g2); g2 = TILE_MFMA(w.y, wt[1], g2); g2 = TILE_MFMA(w.z, wt[2], g2); g2 = TILE_MFMA(w.w, wt[3], g2);
-    }
-#pragma unroll
-    for (int v = 0; v < 16; v++) g2[v] = a2[v] > 0.0f ? g2[v] : 0.0f;
-    aop(wimg, AG_W2T, lane, aw);
-#pragma unroll
-    for (int v = 0; v < 16; v++) g1 = TILE_MFMA(aw[v], g2[v], g1);
-#pragma unroll
-    for (int v = 0; v < 16; v++) g1[v] = a1[v] > 0.0f ? g1[v] : 0.0f;
-    float ta_[16], tb_[16];
-    put(t0, g2, c, h); put(t1, a1, c, h);
-    wave_lds_sync();
-    get(t0, ta_, c, h); get(t1, tb_, c, h);
-    wave_lds_sync();
-#pragma unroll
-    for (int s = 0; s < 16; s++) { gW2 = TILE_MFMA(ta_[s], tb_[s], gW2); gb2 += ta_[s]; }
-    put(t0, g1, c, h);
-    wave_lds_sync();
-    get(t0, ta_, c, h);
-    wave_lds_sync();
-#pragma unroll
-    for (int s = 0; s < 16; s++) gW1 = TILE_MFMA(ta_[s], xt[s], gW1);
-    put(t0, wt, c, h); put(t1, a2, c, h);
-    wave_lds_sync();
-    get(t0, ta_, c, h); get(t1, tb_, c, h);
-    wave_lds_sync();
-#pragma unroll
-    for (int s = 0; s < 16; s++) { gW3 = TILE_MFMA(ta_[s], tb_[s], gW3); gb3 += ta_[s]; }
+    for (int v = 0; v < 4; v++) wt[v] = (t.valid && v + 4 * h < A) ? -da[v] * (1.0f - mu[v] * mu[v]) : 0.0f;
+    actor_reverse<1>(wimg, AG_W2T, AG_W3T, a1, a2, wt, t.xt, t0, t1, lane, c, h, acc);
   }
 #pragma unroll
   for (int m = 16; m >= 1; m >>= 1) sq += __shfl_xor(sq, m, 64);
-  gb2 += __shfl_xor(gb2, 32, 64); gb3 += __shfl_xor(gb3, 32, 64);
   __syncthreads();
   float* red = tilemem + wave * NROW;
-#pragma unroll
-  for (int v = 0; v < 16; v++) {
-    const int r = row_of(v, h);
-    red[S::A_W2 + r * H + c] = gW2[v];
-    if (c < D) red[S::A_W1 + r * D + c] = gW1[v];
-    if (c == D) red[S::A_B1 + r] = gW1[v];
-    if (r < A) red[S::A_W3 + r * H + c] = gW3[v];
-  }
-  if (h == 0) red[S::A_B2 + c] = gb2;
-  if (h == 0 && c < A) red[S::A_B3 + c] = gb3;
+  actor_row<S, D, A, K_OUT>(acc, red, c, h);
   if (lane == 0) red[S::NPA] = sq;
   __syncthreads();
   reduce_rows<NROW>(tilemem, partial + (size_t)blockIdx.x * NROW);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- apply
-// g = scale * (rows of partial added in order);  Lasagne's Adam on the live network (tu_pg.hip: pg_adam_kernel);  target <- (1 - tau) target
-// + tau live;  stats[k] += the row sums of the `ns` columns behind the gradient (float64).  One workgroup.
-struct Offsets { int o[7]; };   // starts of W1, b1, W2, b2, W3, b3 in the row, and the parameter count
+// apply_rows (mlp32_tiles.h) on one network: Adam on the live network, the soft update of its target, the statistic columns.  One workgroup.
 __global__ void __launch_bounds__(1024) apply_kernel(int rows, int ns, const float* __restrict__ partial, float scale, NetRW live, NetRW targ, Offsets off,
                                                      float* __restrict__ m, float* __restrict__ v, float a, float beta1, float beta2, float eps, float tau,
                                                      double* __restrict__ stats) {
-  apply_rows(rows, ns, partial, scale, live, targ, off.o, m, v, a, beta1, beta2, eps, tau, stats);   // mlp32_tiles.h
+  apply_rows(rows, ns, partial, scale, live, targ, off.o, m, v, a, beta1, beta2, eps, tau, stats);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- policy step
-// tu_trpo.hip's policy_step_mfma_kernel with ReLU hidden units, a tanh output and Ornstein-Uhlenbeck noise (rllab's OUStrategy):
+// policy_step (mlp32_tiles.h) with a tanh output and Ornstein-Uhlenbeck noise (rllab's OUStrategy):
 //   x = path_t == 0 ? mu : ou;  x += theta (mu - x) + sigma noise;  act = clip(mu(s) + x, -1, 1)
-// obs32 and act are the pool's rows [top, top + n) (the caller passes the offset pointers).
 template <int D, int A>
 __global__ void __launch_bounds__(64 * WAVES, 2) policy_step_kernel(const double* __restrict__ obs, int n, Net th, const float* __restrict__ noise,
                                                                     const long long* __restrict__ path_t, float ou_theta, float ou_sigma, float ou_mu,
                                                                     float* __restrict__ ou, const double* __restrict__ low, const double* __restrict__ high,
                                                                     float* __restrict__ obs32, float* __restrict__ act, double* __restrict__ env_act) {
-  constexpr int KS1 = (D + 1) / 2;
-  __shared__ alignas(16) float sbias[3][32];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, h = lane >> 5;
-  if (tid < 32) { sbias[0][tid] = th.b1[tid]; sbias[1][tid] = th.b2[tid]; sbias[2][tid] = tid < A ? th.b3[tid] : 0.0f; }
-  float aW1[KS1], aW2[16], aW3[16];
-  double lo[4], hi[4];
-#pragma unroll
-  for (int s = 0; s < KS1; s++) aW1[s] = wel<D, A>(K_FIRST, th.W1, s, c, h);
-#pragma unroll
-  for (int v = 0; v < 16; v++) { aW2[v] = wel<D, A>(K_HID, th.W2, v, c, h); aW3[v] = wel<D, A>(K_OUT, th.W3, v, c, h); }
-#pragma unroll
-  for (int v = 0; v < 4; v++) { const int a = v + 4 * h; lo[v] = a < A ? low[a] : 0.0; hi[v] = a < A ? high[a] : 0.0; }
-  __syncthreads();
-  const int tl = blockIdx.x * WAVES + wave;   // one tile per wavefront
-  const int smp = tl * 32 + c;
-  const bool valid = smp < n;
-  float xb[KS1];
-#pragma unroll
-  for (int s = 0; s < KS1; s++) {
-    const int k = 2 * s + h;
-    const bool on = valid && k < D;
-    xb[s] = on ? (float)obs[(size_t)smp * D + k] : 0.0f;
-    if (on) obs32[(size_t)smp * D + k] = xb[s];
-  }
-  v16f h1 = bias_tile(sbias[0], h);
-#pragma unroll
-  for (int s = 0; s < KS1; s++) h1 = TILE_MFMA(aW1[s], xb[s], h1);
-  relu16(h1);
-  v16f h2 = bias_tile(sbias[1], h);
-#pragma unroll
-  for (int v = 0; v < 16; v++) h2 = TILE_MFMA(aW2[v], h1[v], h2);
-  relu16(h2);
-  v16f z3 = bias_tile(sbias[2], h);
-#pragma unroll
-  for (int v = 0; v < 16; v++) z3 = TILE_MFMA(aW3[v], h2[v], z3);
-  const bool fresh = valid && path_t[smp] == 0;
-#pragma unroll
-  for (int v = 0; v < 4; v++) {
-    const int a = v + 4 * h;
-    if (valid && a < A) {
-      const size_t o = (size_t)smp * A + a;
-      float x = fresh ? ou_mu : ou[o];
-      x = x + ou_theta * (ou_mu - x) + ou_sigma * noise[o];
-      ou[o] = x;
-      float val = tanh_fast(z3[v]) + x;
-      val = val < -1.0f ? -1.0f : (val > 1.0f ? 1.0f : val);
-      act[o] = val;
-      double e = lo[v] + ((double)val + 1.0) * 0.5 * (hi[v] - lo[v]);
-      e = e < lo[v] ? lo[v] : (e > hi[v] ? hi[v] : e);
-      env_act[o] = e;
-    }
-  }
+  policy_step<D, A, K_OUT>(obs, n, th, low, high, obs32, act, env_act, [&](const v16f& z3, int v, size_t o, int smp) {
+    float x = path_t[smp] == 0 ? ou_mu : ou[o];
+    x = x + ou_theta * (ou_mu - x) + ou_sigma * noise[o];
+    ou[o] = x;
+    const float val = tanh_fast(z3[v]) + x;
+    return val < -1.0f ? -1.0f : (val > 1.0f ? 1.0f : val);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- pool commit
@@ -402,9 +210,10 @@ extern "C" {
 
 int CassieDdpgParamCount(int obs_dim, int act_dim, int which) {
   if (!cassie_ddpg::shape_ok(obs_dim, act_dim)) return 0;
-  if (which == CASSIE_DDPG_ACTOR) return 32 * obs_dim + 32 + 32 * 32 + 32 + act_dim * 32 + act_dim;
-  if (which == CASSIE_DDPG_CRITIC) return 32 * obs_dim + 32 + 32 * (32 + act_dim) + 32 + 32 + 1;
-  return 0;
+  int off[7] = {0};
+  if (which == CASSIE_DDPG_ACTOR) cassie_ddpg::actor_offsets(obs_dim, act_dim, off);
+  else if (which == CASSIE_DDPG_CRITIC) cassie_ddpg::critic_offsets(obs_dim, act_dim, off);
+  return off[6];
 }
 int CassieDdpgPartialRows(int batch) { return batch > 0 ? cassie_ddpg::blocks_for(batch) : 0; }
 
