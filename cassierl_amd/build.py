@@ -2,7 +2,7 @@
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on
 the MI355X box.  The shared object is kept in cassierl_amd/lib/ (git-ignored, shipped by gpurun).
-One translation unit per kernel family (csrc/tu_*.hip + the C-ABI in cassie_cabi.hip), compiled
+One translation unit per kernel family (csrc/tu_*.hip + the C-ABI in cassie_cabi.hip / cassie3d_cabi.hip), compiled
 in parallel to objects under lib/obj/ and linked into one shared library.
 """
 import os
@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "libcassie2d.so")
-UNITS = ["cassie_cabi", "tu_base", "tu_g16", "tu_leg", "tu_leg_seg", "tu_duo", "tu_duo_hf", "tu_hf", "tu_ctrl", "tu_ctrl_g16", "tu_3d", "tu_trpo", "tu_trpo_baseline", "tu_pg", "tu_pg_trpo", "tu_ddpg", "tu_ppo", "tu_sac", "tu_td3", "tu_es", "tu_es_wide"]
+UNITS = ["cassie_cabi", "tu_base", "tu_g16", "tu_leg", "tu_leg_seg", "tu_duo", "tu_duo_hf", "tu_hf", "tu_ctrl", "tu_ctrl_g16", "tu_3d", "tu_trpo", "tu_trpo_baseline", "tu_pg", "tu_pg_trpo", "tu_ddpg", "tu_ppo", "tu_sac", "tu_td3", "tu_es", "tu_es_wide", "cassie3d_cabi"]
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"] + os.environ.get("CASSIE_HIPCC_FLAGS", "").split()
