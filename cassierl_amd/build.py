@@ -224,7 +224,9 @@ def build_guards(verbose=False):
     libs = {n: build_variant(n, u, f, verbose) for n, (u, f) in sorted(GUARD_VARIANTS.items())}
     # the pattern build of tu_duo exactly as the compiler emits it, NOT passed through the ISA guard: with hipcc 7.2.0 its env_step_duo_kernel<1> holds
     # the exec-hole copy and is wrong on the GPU (the guard's known-bad reference: tests/test_isa_guard.py, tests/test_gpu_build_guard.py)
-    libs["avi_pattern_raw"] = build_variant("avi_pattern_raw", ["tu_duo"], ["-ftrivial-auto-var-init=pattern"], verbose, guarded=False)
+    # (-DCASSIE_DUO_STORED_ROWS: the kernel's hand-over in the form the defect was found with, cassie_duo_core.h -- with the direct path the allocator
+    # happens to split elsewhere and the unguarded pattern build is clean, which would leave the guard without its reference)
+    libs["avi_pattern_raw"] = build_variant("avi_pattern_raw", ["tu_duo"], ["-ftrivial-auto-var-init=pattern", "-DCASSIE_DUO_STORED_ROWS"], verbose, guarded=False)
     return libs
 
 

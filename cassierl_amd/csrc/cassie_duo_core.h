@@ -16,7 +16,10 @@
 // The phases are INDEPENDENT: everything a group carries from its set-up to the joint sweep and on to its finish (state, rows, factorisation,
 // forces) goes through a per-wavefront workspace in global memory, stored at the end of a phase and loaded in one batch at the head of the next
 // (the set-up needs the whole register file; see "hand-over" below and DESIGN.md section 5 K1d for the builds that tried otherwise).  Set-up and
-// finish exist once, in a loop over the two groups.
+// finish exist once, in a loop over the two groups.  ONE exception, the direct path (env_step2): group B is set up last, so when it ends on its
+// feet and group A is not in the eight-row format its 68 row words stay in registers and the joint solve runs right behind its set-up, on A's loaded
+// rows and B's rows in place -- a fifth of the hand-over's accesses never happen (65 536 walk / PD envs: 0.973 -> 0.930 ms per step).  Every other
+// combination of the two groups takes the stand-alone block, so `joint_sweeps` is instantiated twice.
 //
 // The arithmetic of an environment is the arithmetic of cassie_leg_core.h operation for operation: the set-up and the finish ARE its
 // functions (`sub_setup`, `sub_finish`), the joint sweep executes the owner lane's sequence of the pair sweep (same step functions
@@ -303,6 +306,10 @@ template <class B> struct Duo : Core<B> {
     lfor<0, NP>([&](auto pp) { constexpr int P = decltype(pp)::value; s.Ant[P] = 0.0; });
   }
 
+  // -DCASSIE_DUO_STORED_ROWS (A/B builds; the ISA guard's known-bad reference build, cassierl_amd/build.py): group B's rows always go through the
+  // workspace, as before the direct path (env_step2).  The sites under this macro keep that form's source word for word, so such a build compiles to
+  // that kernel -- the register allocation of this kernel, and with it the compiler defect the guard exists for, follow the smallest change of the text.
+#ifdef CASSIE_DUO_STORED_ROWS
   // One joint solve for the groups of `join` (wave-uniform flags): rows in, forces and iteration counts back in the groups' Sub.
   static LEG_FN void joint_solve(Sub (&S)[2], const bool (&join)[2]) {
     const M even = B::leg() == I(0);
@@ -331,6 +338,37 @@ template <class B> struct Duo : Core<B> {
     }
   }
 
+#else
+  // One joint solve for the groups of `join` (wave-uniform flags): rows in, forces and iteration counts back in the groups' Sub.  The two groups
+  // come by reference, not as an array: on the direct path (env_step2) SB IS the Sub group B's set-up has just filled.
+  static LEG_FN void joint_solve(Sub& SA, Sub& SB, const bool (&join)[2]) {
+    const M even = B::leg() == I(0);
+    const M none = even & !even;
+    // environments of a group that does not take part never sweep (their lanes hold whatever that group's set-up left)
+    const M goA = join[0] ? SA.go : none, goB = join[1] ? SB.go : none;
+    LegRows L, R;
+    gather<0>(even, SA, SB, L);
+    gather<1>(even, SA, SB, R);
+    D a0 = B::sel(even, SA.a0, SB.a0), a1 = B::sel(even, SA.a1, SB.a1), a2 = B::sel(even, SA.a2, SB.a2);   // a~ is the same on both lanes of a pair
+    const M go = (even & goA) | ((!even) & goB);
+    I niter;
+    B::fence();
+    joint_sweeps(L, R, a0, a1, a2, go, niter);
+    B::fence();
+    // forces back to the leg lanes: group A's left legs sit on the even lanes (own L), its right legs on the odd lanes (partner's R);
+    // group B's left legs on the even lanes (partner's L), its right legs on the odd lanes (own R)
+    const I nsw = B::swapi(niter);
+    if (join[0]) {
+      lfor<0, NR>([&](auto ii) { constexpr int Ii = decltype(ii)::value; SA.f[Ii] = B::sel(even, L.f[Ii], B::swap(R.f[Ii])); });
+      SA.niter = B::seli(even, niter, nsw);
+    }
+    if (join[1]) {
+      lfor<0, NR>([&](auto ii) { constexpr int Ii = decltype(ii)::value; SB.f[Ii] = B::sel(even, B::swap(L.f[Ii]), R.f[Ii]); });
+      SB.niter = B::seli(even, nsw, niter);
+    }
+  }
+
+#endif
 #ifdef DUO_VIEW_EXPERIMENT
   // ---- r05 EXPERIMENT, kept as source for the build guard (tests/test_gpu_build_guard.py, DESIGN.md section 5 K1d "dead-code dependence"): the joint
   // sweep's rows transposed by the ADDRESSES of the hand-over instead of lane exchanges.  Joint lane 2e + k (environment e of group k) reads its LEFT
@@ -651,6 +689,9 @@ template <class B> struct Duo : Core<B> {
   // (profiling builds: a backend whose Lds keeps the reset pass's clocks apart is told where that pass begins and ends; any other Lds is not)
   template <class L> static LEG_FN auto in_reset_pass(L& l, bool on, int) -> decltype(l.in_reset_pass(on)) { return l.in_reset_pass(on); }
   template <class L> static LEG_FN void in_reset_pass(L&, bool, long) {}
+  // (device backend: a row word as a NEW value, unknown to the optimiser, where the direct path begins -- see there; any other backend: nothing)
+  template <class Bk> static LEG_FN auto fresh(D& v, int) -> decltype(Bk::fresh(v)) { return Bk::fresh(v); }
+  template <class Bk> static LEG_FN void fresh(D&, long) {}
   template <int MODE, bool HF = false, class IoOf>
   static LEG_FN void env_step2(const EnvCfg& cfg, typename B::Lds& lds, W ws, IoOf&& io_of, const M (&valid)[2], Out (&o)[2], const Terrain* hf = nullptr) {
 #ifdef CASSIE_TWO_OUTPUTS   // A/B and profiling builds: the generic form (reset pass, then a second outputs call) on the flat floor too
@@ -706,6 +747,9 @@ template <class B> struct Duo : Core<B> {
     while (true) {
       bool join[2] = {false, false}, ran[2] = {false, false};
       bool join8[2] = {false, false};   // the group's rows are in the workspace in the eight-row format (r06: the eight-row joint sweep)
+#ifndef CASSIE_DUO_STORED_ROWS
+      bool direct = false;              // group B's rows went straight into the joint sweep (below): phase 2 is done when phase 1 ends
+#endif
       M ovf[2] = {none, none};
       I nit[2] = {I(0), I(0)};
       lds.snapshot(reset_pass || sub == cfg.n_sub - 1);
@@ -731,11 +775,40 @@ template <class B> struct Duo : Core<B> {
           SubOut so;
           // The rows leave for the workspace INSIDE the branch of the set-up that built them (six slots on their feet / eight): with B::SPLIT_TAIL the two
           // cases never meet again, so nothing of a row has to survive a merge of the two paths (and a group on its feet does not build its two empty slots).
+#ifdef CASSIE_DUO_STORED_ROWS
           auto rows_small = [&]() {
             B::fence();
             put_rows(ws, base, S); put_keep(ws, base, S); put_misc(ws, base, S.go, S.ncon);
             lds.mark(10);   // 10 = rows / factorisation out
           };
+#else
+          // DIRECT PATH: group B is set up last and nothing runs between its set-up and the joint sweep, so when B ends in the six-row tail and A
+          // is not in the eight-row format (it joined six-row, or does not run in this pass) B's 68 row words never see the workspace: the tail
+          // stores what B's finish needs, and right behind the set-up A's rows come in and the joint solve runs on A's loaded rows and B's rows in
+          // place -- 34 sixteen-byte stores and the 34 loads that fetched them back a few hundred instructions later are gone (136 of a pass's 616
+          // slot accesses).  The condition is wave-uniform and known before B's set-up starts; every other combination takes the stand-alone block of
+          // phase 2.  What the register allocation asks for (each measured): the factorisation leaves BEFORE the tail
+          // branches (words both branches store stay live through whichever comes first in the layout: 150 accumulator-file reads per sweep
+          // instead of 67); the row words enter the direct path as new values (B::fresh); and the solve stands behind the set-up's return, not
+          // inside its tail (inside: 517 / 574 instructions per sweep, 260 B of scratch; behind: 500 / 536 and 152 B).
+          bool go_direct = g == 1 && !join8[0];
+#ifdef DUO_VIEW_EXPERIMENT
+          if (cfg.flags & CASSIE_DUO_VIEW_FLAG) go_direct = false;   // (joint_solve_view reads both groups' rows from the workspace)
+#endif
+          auto rows_small = [&]() {
+            B::fence();
+            put_keep(ws, base, S); put_misc(ws, base, S.go, S.ncon);
+            B::fence();
+            if (go_direct) {
+              lds.mark(10);   // 10 = rows / factorisation out (here: B's factorisation alone)
+              rows_each(S, 0, [&](int, D& v) { fresh<B>(v, 0); });
+              direct = true;
+            } else {
+              put_rows(ws, base, S);
+              lds.mark(10);   // 10 = rows / factorisation out
+            }
+          };
+#endif
           auto rows_general = [&]() {
             // some environment of the group has a joint limit active or a third pair: all eight row slots go to the workspace, with what the finish
             // needs of the once-per-wavefront descriptors, for the eight-row joint sweep
@@ -747,6 +820,27 @@ template <class B> struct Duo : Core<B> {
           C::template sub_setup<MODE, HF>(lds, st, reset_pass || MODE == 2, lv, !reset_pass, so, S, hf, rows_small, rows_general);
           ovf_ = so.overflow;
           B::fence();
+#ifndef CASSIE_DUO_STORED_ROWS
+          if (direct) {
+            Sub SA;
+            if (join[0]) { get_rows(ws, 0, SA); get_misc(ws, 0, SA.go, SA.ncon); }
+            else idle_rows(SA);
+            B::fence();
+            lds.mark(11);   // 11 = rows in (here: A's alone)
+            const bool jn[2] = {join[0], true};
+            joint_solve(SA, S, jn);
+            B::fence();
+            lds.mark(7);    // 7 = transpose + joint sweeps + forces back
+            if (join[0]) {
+              put_forces(ws, 0, SA);
+              B::wst(ws, W_MISC + 2, B::toD(SA.niter));
+            }
+            put_forces(ws, base, S);
+            B::wst(ws, base + W_MISC + 2, B::toD(S.niter));
+            B::fence();
+            lds.mark(12);   // 12 = forces out
+          }
+#endif
           if (S.small) join_ = true;
           else join8_ = true;
           B::fence();
@@ -773,7 +867,12 @@ template <class B> struct Duo : Core<B> {
         B::fence();
         lds.mark(7);
       }
+#ifdef CASSIE_DUO_STORED_ROWS
       if (!eight && (join[0] || join[1])) {
+#else
+      if (!eight && !direct && (join[0] || join[1])) {
+        // (the stand-alone block: group B does not run in this pass, or the view experiment is on; with B on the direct path this is done already)
+#endif
         Sub S[2];
         lds.mark(0);
         lfor<0, 2>([&](auto gg) {
@@ -788,7 +887,11 @@ template <class B> struct Duo : Core<B> {
         else
 #endif
         {
+#ifdef CASSIE_DUO_STORED_ROWS
         joint_solve(S, join);
+#else
+        joint_solve(S[0], S[1], join);
+#endif
         B::fence();
         lds.mark(7);    // 7 = transpose + joint sweeps + forces back
         lfor<0, 2>([&](auto gg) {

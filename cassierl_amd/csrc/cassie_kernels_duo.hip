@@ -38,6 +38,8 @@ struct DevDuoB : DevB {
   // set-up's two branches end in their own stores to the workspace and never meet again: 304 B of scratch instead of 264, **1.018 -> 0.990 ms** per 65 536-env
   // step (tools/ab_bench.py, both orders), bit-identical.
   static constexpr bool SPLIT_TAIL = true;
+  // a row word of group B where the direct path begins (Duo::env_step2): the same bits as a new value, so that its live range starts there and not in the set-up
+  static LEG_FN void fresh(double& x) { asm volatile("" : "+v"(x)); }
   // per-wavefront workspace in global memory (Duo::W_*): [slot][lane], the lane's pointer is the base of its column
   // Buffer addressing: one resource descriptor per wavefront (SGPRs), the lane's byte offset in ONE VGPR, the slot as the scalar offset
   // of the instruction -- so a slot costs an s_mov, not a 64-bit per-lane pointer (with plain pointers the compiler materialises one
