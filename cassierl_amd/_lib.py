@@ -13,6 +13,11 @@ class CassieVecConfig(ct.Structure):
                 ("flags", ct.c_int), ("auto_reset", ct.c_int)]
 
 
+class Cassie3dEnvConfig(ct.Structure):
+    _fields_ = [("control_mode", ct.c_int), ("n_substeps", ct.c_int), ("auto_reset", ct.c_int),
+                ("kp", ct.c_double * 10), ("kd", ct.c_double * 10)]
+
+
 EXPORTS = [
     # legacy ABI (include/cassie2d.h)
     "Cassie2dInit", "Reset", "StepOsc", "StepTorque", "StepJacobian", "StepPd", "GetGeneralState",
@@ -27,6 +32,7 @@ EXPORTS = [
     "Cassie3dVecCreate", "Cassie3dVecFree", "Cassie3dVecLastError", "Cassie3dVecSetStream", "Cassie3dVecSynchronize",
     "Cassie3dVecReset", "Cassie3dVecStep", "Cassie3dVecStatePtr", "Cassie3dVecGetCounters", "Cassie3dVecResetCounters", "Cassie3dVecStepHost", "Cassie3dVecGetStateHost",
     "Cassie3dVecSetStateHost", "Cassie3dVecDebugForwardHost", "Cassie3dVecTimeSteps",
+    "Cassie3dVecEnvConfigure", "Cassie3dVecSubstepPd", "Cassie3dVecEnvReset", "Cassie3dVecEnvStep", "Cassie3dVecEnvStepHost", "Cassie3dVecEnvGetCounters",
     # fused policy kernels of the TRPO outer loop (include/cassie_trpo.h)
     "CassieTrpoParamCount", "CassieTrpoPartialRows", "CassieTrpoFvp", "CassieTrpoVjp", "CassieTrpoSurrogate", "CassieTrpoCgUpdate", "CassieTrpoPolicyStep", "CassieTrpoSamplerRows", "CassieTrpoSamplerStep",
     "CassieTrpoBaselineFeatures", "CassieTrpoBaselinePredict", "CassieTrpoReturnsAdvantages", "CassieTrpoGramRows", "CassieTrpoGramRowSize", "CassieTrpoBaselineGram", "CassieTrpoRidgeSolve",
@@ -128,6 +134,13 @@ def load():
     L.Cassie3dVecSetStateHost.argtypes = [vp, dp]
     L.Cassie3dVecDebugForwardHost.argtypes = [vp, dp, dp]
     L.Cassie3dVecTimeSteps.argtypes = [vp, dp, ct.c_int, ct.c_int, ct.POINTER(ct.c_float)]
+    if hasattr(L, "Cassie3dVecEnvStep"):   # (absent from A/B libraries built from earlier sources: CASSIE2D_LIB)
+        L.Cassie3dVecEnvConfigure.argtypes = [vp, ct.POINTER(Cassie3dEnvConfig)]
+        L.Cassie3dVecSubstepPd.argtypes = [vp, dp, ct.c_int]
+        L.Cassie3dVecEnvReset.argtypes = [vp, u8p, dp]
+        L.Cassie3dVecEnvStep.argtypes = [vp, dp, dp, dp, u8p, dp]
+        L.Cassie3dVecEnvStepHost.argtypes = [vp, dp, dp, dp, u8p, dp]
+        L.Cassie3dVecEnvGetCounters.argtypes = [vp, ct.POINTER(ct.c_uint64)]
     L.Cassie2dInit.restype = ct.c_void_p
     _LIB = L
     return L

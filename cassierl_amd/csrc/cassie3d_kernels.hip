@@ -298,7 +298,7 @@ __device__ __forceinline__ void kin_mass3(Smem3<MR>& sm, int lane, double& bias_
 struct Out3 { int niter, nefc; bool overflow, capped; };
 
 // ---------------------------------------------------------------- one mj_forward (+ Euler step) of one environment
-template <int MR, bool CAP>
+template <int MR, bool CAP, bool PD = false>   // (PD: no effect on the code; every kernel keeps a substep with one caller, as before PD mode existed)
 __device__ void substep3(Smem3<MR>& sm, int lane, double ctrl_l /* dof lane: command of its motor, pre-clamp */, bool integrate, Out3& out, double* dbg) {
   double bias;
   kin_mass3(sm, lane, bias, dbg);
@@ -661,12 +661,15 @@ __device__ void substep3(Smem3<MR>& sm, int lane, double ctrl_l /* dof lane: com
   }
 }
 
-// ---------------------------------------------------------------- n_sub torque-mode substeps of every environment
+// ---------------------------------------------------------------- n_sub substeps of every environment
 // Two instantiations are launched back to back (cassie_cabi.hip): <MAXR_FAST, 2> does every environment that needs at most 32
 // constraint rows at twice the occupancy and hands the others over through `pending` (substeps left, state saved at that
 // point); <MAXR, 1> finishes those and returns at once for everyone else.
-template <int MR, int WPS>
-__global__ void __launch_bounds__(64, WPS) env_step3d_kernel(Params3 p) {
+// PD = false: torque mode, p.actions are the motor commands.  PD = true: p.actions are joint targets and the dof lane of actuator a
+// commands kp_a (target_a - q) - kd_a v from the state at the start of every substep (p.pd_gains = kp[NU] kd[NU]; Cassie2d.cpp:96-117);
+// a robot handed over mid-step is finished with the same law from its saved state.
+template <int MR, int WPS, bool PD = false>
+__global__ void __launch_bounds__(64, WPS) env_step3d_kernel(typename Params3Of<PD>::type p) {
   __shared__ Smem3<MR> sm;
   constexpr bool CAP = MR == MAXR;  // the general kernel is the last resort: it caps instead of handing over
   const int env = blockIdx.x, lane = threadIdx.x;
@@ -684,13 +687,16 @@ __global__ void __launch_bounds__(64, WPS) env_step3d_kernel(Params3 p) {
   const int a = lane < NV ? c3_dof_act[lane] : -1;
   double ctrl_l = 0.0;
   if (a >= 0) ctrl_l = p.actions ? p.actions[(size_t)env * NU + a] : st[E3_CTRL + a];
+  double tgt = 0.0, kp = 0.0, kd = 0.0;
+  if constexpr (PD) { tgt = ctrl_l; if (a >= 0) { kp = p.pd_gains[a]; kd = p.pd_gains[NU + a]; } }
   lds_sync();
   Out3 out; out.niter = 0; out.nefc = 0; out.overflow = false; out.capped = false;
   int niter_sum = p.pending_in ? (int)st[E3_NITER] : 0;
   double* dbg = p.debug ? p.debug + (size_t)env * D3_STRIDE : nullptr;
   int left = 0, ncapped = 0;
   for (int sub = 0; sub < n_sub; sub++) {
-    substep3<MR, CAP>(sm, lane, ctrl_l, p.integrate != 0, out, dbg);
+    if constexpr (PD) { if (a >= 0) ctrl_l = kp * (tgt - sm.q[lane + 1]) - kd * sm.v[lane]; }   // the hinge of dof d is qpos[d + 1]
+    substep3<MR, CAP, PD>(sm, lane, ctrl_l, p.integrate != 0, out, dbg);
     if (out.overflow) { left = n_sub - sub; break; }  // (never with CAP) detected before anything of this substep was written
     niter_sum += out.niter;
     ncapped += out.capped ? 1 : 0;

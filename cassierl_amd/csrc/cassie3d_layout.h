@@ -29,10 +29,31 @@ struct Params3 {
   int* gone;
   int seg_first, seg_later;
 };
+// ... of the PD instantiations of the kernels: `actions` holds joint targets, pd_gains = kp[NU] kd[NU].  A type of its own, so that the
+// torque-mode kernels keep the parameter block -- and with it the register allocation -- they had before PD mode existed.
+struct Params3Pd : Params3 {
+  const double* pd_gains;
+};
+template <bool PD> struct Params3Of { typedef Params3 type; };
+template <> struct Params3Of<true> { typedef Params3Pd type; };
 // S3_GENERAL_SUBSTEPS: env-substeps the 32-row kernel handed to the 64-row kernel; S3_CAPPED_SUBSTEPS: env-substeps in which
 // the 64-row kernel had to leave contacts out (more than 64 constraint rows)
 // S3_LEG_HANDOVER_SUBSTEPS: env-substeps the lane-per-leg kernel handed to the wavefront-per-environment kernels (row capacity)
 enum { S3_GENERAL_SUBSTEPS = 0, S3_CAPPED_SUBSTEPS = 1, S3_LEG_HANDOVER_SUBSTEPS = 2, S3_N = 4 };
+
+// parameter block of the environment layer's finish kernel (cassie3d_env.hip): observation, reward, done, auto-reset after a step
+struct EnvFinish3 {
+  double* state;              // [n][ENV3_STRIDE]
+  const double* actions;      // [n][10] the rows the caller passed to the step
+  const double* reset_rec;    // [ENV3_STRIDE] the record a reset leaves
+  double* obs;                // [n][45]
+  double* reward;             // [n]
+  unsigned char* done;        // [n]
+  double* terminal_obs;       // [n][45] or null
+  unsigned long long* counters;   // [ENVC_N]
+  int n_envs, auto_reset;
+};
+enum { ENVC_DONE = 0, ENVC_GUARD = 1, ENVC_N = 2 };   // done flags raised; of those by the failure guard
 
 }  // namespace cassie3d
 #endif

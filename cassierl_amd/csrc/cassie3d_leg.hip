@@ -90,8 +90,10 @@ struct DevB3 {
 
 // pending_out[env] = substeps this kernel did NOT do because the environment needed more constraint rows than a lane's LDS slots hold
 // (0 normally); env_step3d_kernel finishes those (cassie_cabi.hip).
-template <int LANES>
-__global__ void __launch_bounds__(64, 1) env_step3d_leg_kernel(Params3 p) {
+// PD: p.actions holds joint targets and every substep's commands come from the PD law (Core3::env_step<true>, gains p.pd_gains); the torque
+// instantiation never reads p.pd_gains.
+template <int LANES, bool PD = false>
+__global__ void __launch_bounds__(64, 1) env_step3d_leg_kernel(typename Params3Of<PD>::type p) {
   typedef Core3<DevB3<LANES>> DCore3;
   __shared__ typename DevB3<LANES>::Lds lds;
   const int lane = threadIdx.x;
@@ -104,9 +106,10 @@ __global__ void __launch_bounds__(64, 1) env_step3d_leg_kernel(Params3 p) {
   io.rec = p.state + e * ENV3_STRIDE;
   io.has_act = p.actions != nullptr;
   io.act = io.has_act ? const_cast<double*>(p.actions) + e * NU : io.rec;
+  if constexpr (PD) io.gains = p.pd_gains;
   if (lane < LANES) for (int s = 0; s < NSLOT3; s++) lds.a[s][lane] = 0.0;   // a lane only ever reads back what it wrote -- or this
   typename DCore3::Out o;
-  DCore3::env_step(lds, io, valid, p.n_sub, p.integrate != 0, o);
+  DCore3::template env_step<PD>(lds, io, valid, p.n_sub, p.integrate != 0, o);
   if (exists && (lane & 1) == 0) {
     const int pend = (valid && o.pend > 0) ? o.pend + (p.gone ? p.seg_later : 0) : 0;
     if (valid) {

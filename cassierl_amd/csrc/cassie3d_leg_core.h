@@ -415,6 +415,8 @@ template <class B> struct Core3 {
   // cu: motor commands of the own leg's five actuators (hip roll, hip yaw, hip pitch, knee, toe), pre-clamp.  `live` masks the
   // environments that take part (identical on the two lanes of an environment); an environment over the row capacity is reported in
   // out.overflow and left untouched.  integrate = false: mj_forward only (Reset).
+  // (PD has no effect on the code: where the substep is a real function, each kernel keeps its own with one caller)
+  template <bool PD = false>
   static LEG3_SUBSTEP_FN void substep(typename B::Lds& lds, Lane& st, const D (&cu)[5], M live, bool integrate, SubOut& out) {
     const I leg = B::opq(B::leg());
     const KP_ K = B::kbase(leg);
@@ -1017,11 +1019,17 @@ template <class B> struct Core3 {
   struct Io {
     typename B::P rec, act;   // the lane's state record [ENV3_STRIDE], its environment's action row [NU] (or the record's ctrl)
     bool has_act;
+    const double* gains = nullptr;   // PD only: kp[NU] kd[NU] in actuator order, the same table for every lane
   };
   struct Out { I pend, niter, nrows; };
 
-  // n_sub torque-mode substeps (Cassie2d::Step semantics on the 3-D mechanism).  On return o.pend = substeps NOT done because the
-  // environment left the row capacity (its state is untouched from that substep on; the next kernel tier finishes it).
+  // n_sub substeps.  PD = false: torque mode (Cassie2d::Step semantics on the 3-D mechanism), the action row holds the motor commands.
+  // PD = true (Cassie2d::StepPd, Cassie2d.cpp:96-117): the action row holds joint targets and the command of actuator a on hinge d is
+  // kp_a (target_a - q_d) - kd_a v_d from the state at the START of every substep; it takes the clamp-and-gear path of substep() like
+  // any other command.  The lane owns the angles and rates of its leg, so the law needs no pair exchange.
+  // On return o.pend = substeps NOT done because the environment left the row capacity (its state is untouched from that substep on;
+  // the next kernel tier finishes it -- in PD mode with the same law from the saved state).
+  template <bool PD = false>
   static LEG_FN void env_step(typename B::Lds& lds, const Io& io, M valid, int n_sub, bool integrate, Out& o) {
     const I leg = B::leg();
     const I lq = leg * 7 + 7, lv = leg * 7 + 6, la = leg * 5;
@@ -1034,13 +1042,18 @@ template <class B> struct Core3 {
       st.ql[i] = B::pld(io.rec, lq + (E3_Q + i)); st.vl[i] = B::pld(io.rec, lv + (E3_V + i)); st.wl[i] = B::pld(io.rec, lv + (E3_WS + i)); });
     D cu[5];
     lfor<0, 5>([&](auto aa) { constexpr int A_ = decltype(aa)::value; cu[A_] = io.has_act ? B::pld(io.act, la + A_) : B::pld(io.rec, la + (E3_CTRL + A_)); });
+    D tg[5], kp[5], kd[5];   // PD: targets and gains of the own leg's actuators (cu then holds the command of the substep)
+    if constexpr (PD) lfor<0, 5>([&](auto aa) { constexpr int A_ = decltype(aa)::value;
+      tg[A_] = cu[A_]; kp[A_] = B::ldc(io.gains, la + A_); kd[A_] = B::ldc(io.gains, la + (NU + A_)); });
     M live = valid;
     o.pend = 0; o.niter = 0; o.nrows = 0;
     D time = B::pld(io.rec, I(E3_TIME));
     SubOut so;
     for (int sub = 0; sub < n_sub; sub++) {
       if (!B::any(live)) break;
-      substep(lds, st, cu, live, integrate, so);
+      if constexpr (PD) lfor<0, 5>([&](auto aa) { constexpr int A_ = decltype(aa)::value; constexpr int Dd = A_ == 4 ? 5 : A_;
+        cu[A_] = kp[A_] * (tg[A_] - st.ql[Dd]) - kd[A_] * st.vl[Dd]; });
+      substep<PD>(lds, st, cu, live, integrate, so);
       const M ovf = live & so.overflow;
       o.pend = B::seli(ovf, I(n_sub - sub), o.pend);
       live = live & !ovf;

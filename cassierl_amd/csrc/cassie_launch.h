@@ -78,8 +78,11 @@ void ctrl_g16(int ctrl, bool scripted, int n_envs, hipStream_t s, const VecParam
 namespace cassie3d {
 namespace launch {
 // tu_3d.hip
-void step3d(int variant /*0: <MAXR_FAST,3>, 1: <MAXR,1>, 2: two environments per wavefront, 3: one lane per leg (32 per wavefront)*/, int n_envs, hipStream_t s, const Params3& p);
+void step3d(int variant /*0: <MAXR_FAST,3>, 1: <MAXR,1>, 2: two environments per wavefront, 3: one lane per leg (32 per wavefront); pd_gains != null: the PD instantiation of variants 0, 1, 3, 4*/, int n_envs, hipStream_t s, const Params3& p, const double* pd_gains = nullptr);
 void init3d(int n_envs, hipStream_t s, double* state, const double* qpos, const double* qvel);
+// tu_3d_env.hip: the environment layer (cassie3d_env.hip)
+void env_finish3d(hipStream_t s, const EnvFinish3& p);
+void env_reset3d(int n_envs, hipStream_t s, double* state, const uint8_t* mask /*null: all*/, const double* reset_rec, double* obs /*[n][45] or null*/);
 }  // namespace launch
 }  // namespace cassie3d
 #endif

@@ -12,8 +12,17 @@
 namespace cassie3d {
 namespace launch {
 
-void step3d(int variant, int n_envs, hipStream_t s, const Params3& p) {
+void step3d(int variant, int n_envs, hipStream_t s, const Params3& p, const double* pd_gains) {
   dim3 grid(n_envs), block(64);
+  if (pd_gains) {   // PD mode: the same tiers, instantiated with the control law in the substep loop (the pair kernel has none: cassie3d_cabi.hip refuses)
+    Params3Pd pp;
+    static_cast<Params3&>(pp) = p; pp.pd_gains = pd_gains;
+    if (variant == 3) hipLaunchKernelGGL((leg::env_step3d_leg_kernel<32, true>), dim3((n_envs + 15) / 16), block, 0, s, pp);
+    else if (variant == 4) hipLaunchKernelGGL((leg::env_step3d_leg_kernel<64, true>), dim3((n_envs + 31) / 32), block, 0, s, pp);
+    else if (variant == 0) hipLaunchKernelGGL((env_step3d_kernel<MAXR_FAST, C3_FAST_WPS, true>), grid, block, 0, s, pp);
+    else if (variant == 1) hipLaunchKernelGGL((env_step3d_kernel<MAXR, 1, true>), grid, block, 0, s, pp);
+    return;
+  }
   if (variant == 3) hipLaunchKernelGGL(leg::env_step3d_leg_kernel<32>, dim3((n_envs + 15) / 16), block, 0, s, p);   // one lane per leg, 16 environments per wavefront (half of it idle: four wavefronts per CU)
   else if (variant == 4) hipLaunchKernelGGL(leg::env_step3d_leg_kernel<64>, dim3((n_envs + 31) / 32), block, 0, s, p);   // ... 32 environments per wavefront (two per CU): CASSIE3D_LEG=64
   else if (variant == 2) hipLaunchKernelGGL(env_step3d_pair_kernel, dim3((n_envs + 1) / 2), block, 0, s, p);   // two environments per wavefront

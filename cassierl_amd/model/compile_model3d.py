@@ -372,6 +372,12 @@ def emit_kernel_header(mj, tree, consts, links, to_link, dir_to_link, path):
     o.append(_carr("c3_eq_solimp", [e["solimp"] for e in eq], static=S))
     o.append(_carr("c3_qpos0", tree.qpos0, static=S))
     o.append(_carr("c3_qpos_init", QINIT, static=S))
+    # the foot contact sites (left front, left rear, right front, right rear) in their welded link's frame: the environment layer's
+    # foot position (cassie3d_env.h) is the mean of a leg's two
+    foot = [to_link(s["body"], s["pos"]) for s in mj["sites"] if s["name"].endswith(("_contact_front", "_contact_rear"))]
+    o.append("constexpr int NFOOTSITE = %d;\n" % len(foot))
+    o.append(_carr("c3_site_link", [l for l, _ in foot], "%d", "int", 4, S))
+    o.append(_carr("c3_site_pos", [p for _, p in foot], static=S))
     o.append("}  // namespace cassie3d\n#endif\n")
     with open(path, "w") as f:
         f.write("\n".join(o))

@@ -68,6 +68,37 @@ int Cassie3dVecDebugForwardHost(Cassie3dVec* h, const double* torques, double* d
 /* average time of `steps` back-to-back Cassie3dVecStep calls, HIP events on the handle's stream */
 int Cassie3dVecTimeSteps(Cassie3dVec* h, const double* torques_dev, int n_sub, int steps, float* avg_ms);
 
+
+/* ---- The environment layer: an RL environment around the physics, with the vocabulary of CassieVecStep (cassie_vec.h).  The reference
+ * has no Cassie3d environment, so the task is defined here by analogy to its 2-D standing task (rllab/envs/cassie_stand2d.py:118-125):
+ *   observation [CASSIE3D_NOBS]: pelvis z | quaternion w x y z | 14 hinge angles | world linear velocity | body-frame angular velocity |
+ *     14 hinge rates | left foot - pelvis | right foot - pelvis (world axes; a foot = the mean of its two contact sites)
+ *   reward: 1 - 2 (0.9 - z)^2 - 2 fx^2 - 2 fy^2 - 0.001 |action|^2 (fx, fy: mean of the feet's x, y relative to the pelvis)
+ *   done: z < 0.5.  Failure guard: a non-finite qpos / qvel entry or one beyond 1e10: done, reward 0, observation zeros (the reset
+ *     observation with auto-reset).  With auto_reset a done environment's whole record is replaced by the one Cassie3dVecReset(h, NULL,
+ *     NULL) leaves.
+ * CASSIE3D_CTRL_PD: the action row holds targets of the ten actuated hinges; EVERY substep commands kp (target - q) - kd v from the
+ * state at its start (Cassie2d::StepPd, Cassie2d.cpp:96-117), clamped and geared like a torque.  Not available on a handle created under
+ * CASSIE3D_PAIR=1 (CASSIE_EINVAL). */
+#define CASSIE3D_NOBS 45
+#define CASSIE3D_CTRL_TORQUE 0
+#define CASSIE3D_CTRL_PD 1
+typedef struct { int control_mode, n_substeps, auto_reset; double kp[10], kd[10]; } Cassie3dEnvConfig;
+/* before the first Cassie3dVecEnvStep; validates (mode, n_substeps >= 1, auto_reset 0 / 1, gains finite and >= 0); synchronises.
+ * A handle that was never configured has kp = 10, kd = 5 (Cassie3dVecSubstepPd). */
+int Cassie3dVecEnvConfigure(Cassie3dVec* h, const Cassie3dEnvConfig* cfg);
+/* raw PD substeps with the configured gains, no environment layer: n_sub mj_steps towards targets_dev [n][10] */
+int Cassie3dVecSubstepPd(Cassie3dVec* h, const double* targets_dev, int n_sub);
+/* resets the environments with mask_dev[i] != 0 (NULL: all) to the standing pose; obs_dev [n][45] (or NULL) gets EVERY environment's observation */
+int Cassie3dVecEnvReset(Cassie3dVec* h, const uint8_t* mask_dev, double* obs_dev);
+/* one environment step: n_substeps substeps under actions_dev [n][10], then obs [n][45], reward [n], done [n]; terminal_obs_dev [n][45]
+ * (or NULL): the observation of the state the step ended in, before any reset (zeros under the guard) */
+int Cassie3dVecEnvStep(Cassie3dVec* h, const double* actions_dev, double* obs_dev, double* reward_dev, uint8_t* done_dev, double* terminal_obs_dev);
+/* the same with host pointers, synchronous (tests); terminal_obs may be NULL */
+int Cassie3dVecEnvStepHost(Cassie3dVec* h, const double* actions, double* obs, double* reward, uint8_t* done, double* terminal_obs);
+/* out2[0] done flags raised since create; out2[1] of those by the failure guard (synchronises the stream) */
+int Cassie3dVecEnvGetCounters(Cassie3dVec* h, uint64_t* out2);
+
 #ifdef __cplusplus
 }
 #endif
