@@ -47,6 +47,8 @@ EXPORTS = [
     "CassieTd3PolicyStep", "CassieTd3CriticGrad", "CassieTd3CriticApply",
     # PPO (include/cassie_trpo.h)
     "CassieTrpoGae", "CassieTrpoClipGradRows", "CassieTrpoClipGrad", "CassiePgClipGradRows", "CassiePgClipGrad",
+    # PPO at the Cassie3d shape, 45 x 10 (include/cassie_trpo.h)
+    "CassiePg3dParamCount", "CassiePg3dPolicyStep", "CassiePg3dClipGradRows", "CassiePg3dClipGrad",
     # ES (include/cassie_trpo.h)
     "CassieEsParamCount", "CassieEsPairsPerWorkgroup", "CassieEsPolicyStep", "CassieEsBook", "CassieEsGradRows", "CassieEsGrad",
     "CassieEsWideParamCount", "CassieEsWidePairsPerWorkgroup", "CassieEsWidePolicyStep",

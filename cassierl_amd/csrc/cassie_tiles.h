@@ -80,6 +80,12 @@ template <class F> inline int launch_obs(int obs_dim, F&& launch) {
   else return CASSIE_EINVAL;
   return launched();
 }
+// launch_obs plus Cassie3d's 45-wide observation: the baseline kernels (tu_trpo_baseline.hip, tu_ppo.hip's GAE), which are generic in obs_dim
+template <class F> inline int launch_obs3d(int obs_dim, F&& launch) {
+  if (obs_dim != 45) return launch_obs(obs_dim, launch);
+  launch(Int<45>());
+  return launched();
+}
 
 // ---------------------------------------------------------------------------------------------------------------- 32-wide networks
 namespace w32 {

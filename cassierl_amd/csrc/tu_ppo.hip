@@ -347,7 +347,7 @@ int CassieTrpoGae(const float* obs_dev, const long long* t_dev, const double* re
                   const double* coeffs_dev, const double* last_value_dev, double gamma, double lambda, double* returns_dev, double* adv_dev, double* partial_dev,
                   void* stream) {
   if (!obs_dev || !t_dev || !rew_dev || !cut_dev || T <= 0 || n <= 0 || !returns_dev || !adv_dev || !partial_dev) return CASSIE_EINVAL;
-  return cassie_tiles::launch_obs(obs_dim, [&](auto d) {
+  return cassie_tiles::launch_obs3d(obs_dim, [&](auto d) {
     hipLaunchKernelGGL(cassie_ppo::gae_kernel<d()>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, obs_dev, t_dev, rew_dev, cut_dev, T, n, coeffs_dev, last_value_dev,
                        gamma, lambda, returns_dev, adv_dev, partial_dev);
   });

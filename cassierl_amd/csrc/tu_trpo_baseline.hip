@@ -218,20 +218,76 @@ __global__ void __launch_bounds__(64) ridge_solve_kernel(const double* __restric
   if (row) x_out[i] = xs;   // (as the torch loop: after five tries the last attempt's vector, finite or not)
 }
 
+// ridge_solve_kernel's contract for more features than a wavefront has lanes (Cassie3d: F = 94): the lower triangle in LDS (F x (F + 1)
+// doubles, 71 KB at 94), worked by ONE workgroup of 256 lanes -- a right-looking Cholesky (per column: scale it, barrier, rank-one update of
+// the trailing triangle with four lanes per row, barrier), forward substitution by columns, backward substitution by rows of L' (lane i
+// carries the sum of x_i's row), the same retry rule.  Every sum runs in a fixed order; it runs once per iteration.
+template <int F>
+__global__ void __launch_bounds__(256) ridge_solve_lds_kernel(const double* __restrict__ A, const double* __restrict__ b, double reg, double* __restrict__ x_out) {
+  constexpr int LD = F + 1, NT = 256;
+  __shared__ double L[F * LD];
+  __shared__ double vec[F];   // the right-hand side while it becomes y, then x
+  const int tid = threadIdx.x;
+  const bool row = tid < F;
+  double xs = 0.0;
+  for (int attempt = 0; attempt < 5; attempt++, reg *= 10.0) {
+    __syncthreads();   // the previous attempt's reads are done
+    for (int e = tid; e < F * F; e += NT) {
+      const int i = e / F, k = e - i * F;
+      if (k <= i) L[i * LD + k] = A[e] + (k == i ? reg : 0.0);
+    }
+    if (row) vec[tid] = b[tid];
+    __syncthreads();
+    bool bad = false;   // the same value on every lane
+    for (int j = 0; j < F; j++) {
+      const double d = L[j * LD + j];
+      bad = bad || !(d > 0.0) || !(d < 1e300);
+      const double sd = sqrt(bad ? 1.0 : d);
+      __syncthreads();   // every lane has read the pivot
+      for (int i = j + tid; i < F; i += NT) L[i * LD + j] = i == j ? sd : L[i * LD + j] / sd;
+      __syncthreads();
+      for (int i = j + 1 + (tid >> 2); i < F; i += NT / 4) {
+        const double lij = L[i * LD + j];
+        for (int k = j + 1 + (tid & 3); k <= i; k += 4) L[i * LD + k] -= lij * L[k * LD + j];
+      }
+      __syncthreads();
+    }
+    // forward: L y = b, by columns (y_r is finished, the rows below subtract its column)
+    for (int r = 0; r < F; r++) {
+      const double yr = vec[r] / L[r * LD + r];
+      __syncthreads();
+      if (tid == r) vec[r] = yr;
+      if (row && tid > r) vec[tid] -= L[tid * LD + r] * yr;
+      __syncthreads();
+    }
+    // backward: L' x = y, x_r = (y_r - sum_{k > r} L[k][r] x_k) / L[r][r]: lane i < r adds L[r][i] x_r to the sum of its own row
+    double acc = 0.0;
+    for (int r = F - 1; r >= 0; r--) {
+      if (tid == r) { xs = (vec[r] - acc) / L[r * LD + r]; vec[r] = xs; }
+      __syncthreads();
+      if (tid < r) acc += L[r * LD + tid] * vec[r];
+    }
+    const int nonfinite = __syncthreads_or(row && !(fabs(xs) < 1e300));
+    if (!bad && !nonfinite) break;
+  }
+  if (row) x_out[tid] = xs;   // (as the torch loop: after five tries the last attempt's vector, finite or not)
+}
+
 }  // namespace cassie_trpo
 
 extern "C" {
 
-int CassieTrpoBaselineFeatures(int obs_dim) { return (obs_dim == 26 || obs_dim == 17) ? 2 * obs_dim + 4 : 0; }
+int CassieTrpoBaselineFeatures(int obs_dim) { return (obs_dim == 26 || obs_dim == 17 || obs_dim == 45) ? 2 * obs_dim + 4 : 0; }
 int CassieTrpoGramRows(void) { return cassie_trpo::GRAM_BLOCKS * cassie_trpo::GRAM_WAVES; }
 int CassieTrpoGramRowSize(int obs_dim) {
+  if (obs_dim == 45) return cassie_trpo::Feat<45>::NBLK * 256;
   return obs_dim == 26 ? cassie_trpo::Feat<26>::NBLK * 256 : (obs_dim == 17 ? cassie_trpo::Feat<17>::NBLK * 256 : 0);
 }
 
 int CassieTrpoBaselineGram(const float* obs_dev, const long long* t_dev, const double* y_dev, int m, int obs_dim, double* partial_dev, void* stream) {
   if (!obs_dev || !t_dev || !y_dev || m <= 0 || !partial_dev) return CASSIE_EINVAL;
   using namespace cassie_trpo;
-  return cassie_tiles::launch_obs(obs_dim, [&](auto d) {
+  return cassie_tiles::launch_obs3d(obs_dim, [&](auto d) {
     hipLaunchKernelGGL(gram_kernel<d()>, dim3(GRAM_BLOCKS), dim3(64 * GRAM_WAVES), 0, (hipStream_t)stream, obs_dev, t_dev, y_dev, m, partial_dev);
   });
 }
@@ -240,7 +296,7 @@ int CassieTrpoReturnsAdvantages(const float* obs_dev, const long long* t_dev, co
                                 const double* coeffs_dev, const double* last_value_dev, double gamma, double* returns_dev, double* adv_dev, double* partial_dev,
                                 void* stream) {
   if (!obs_dev || !t_dev || !rew_dev || !cut_dev || T <= 0 || n <= 0 || !returns_dev || !adv_dev || !partial_dev) return CASSIE_EINVAL;
-  return cassie_tiles::launch_obs(obs_dim, [&](auto d) {
+  return cassie_tiles::launch_obs3d(obs_dim, [&](auto d) {
     hipLaunchKernelGGL(cassie_trpo::returns_adv_kernel<d()>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, obs_dev, t_dev, rew_dev, cut_dev, T, n, coeffs_dev,
                        last_value_dev, gamma, returns_dev, adv_dev, partial_dev);
   });
@@ -250,13 +306,14 @@ int CassieTrpoRidgeSolve(const double* A_dev, const double* b_dev, int F, double
   if (!A_dev || !b_dev || !x_dev) return CASSIE_EINVAL;
   if (F == 56) hipLaunchKernelGGL(cassie_trpo::ridge_solve_kernel<56>, dim3(1), dim3(64), 0, (hipStream_t)stream, A_dev, b_dev, reg, x_dev);
   else if (F == 38) hipLaunchKernelGGL(cassie_trpo::ridge_solve_kernel<38>, dim3(1), dim3(64), 0, (hipStream_t)stream, A_dev, b_dev, reg, x_dev);
+  else if (F == 94) hipLaunchKernelGGL(cassie_trpo::ridge_solve_lds_kernel<94>, dim3(1), dim3(256), 0, (hipStream_t)stream, A_dev, b_dev, reg, x_dev);
   else return CASSIE_EINVAL;
   return cassie_tiles::launched();
 }
 
 int CassieTrpoBaselinePredict(const float* obs_dev, const long long* t_dev, int m, int obs_dim, const double* coeffs_dev, double* out_dev, void* stream) {
   if (!obs_dev || !t_dev || m <= 0 || !coeffs_dev || !out_dev) return CASSIE_EINVAL;
-  return cassie_tiles::launch_obs(obs_dim, [&](auto d) {
+  return cassie_tiles::launch_obs3d(obs_dim, [&](auto d) {
     hipLaunchKernelGGL(cassie_trpo::predict_kernel<d()>, dim3((m + 255) / 256), dim3(256), 0, (hipStream_t)stream, obs_dev, t_dev, m, coeffs_dev, out_dev);
   });
 }

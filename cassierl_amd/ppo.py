@@ -95,7 +95,7 @@ def clipped_grad_closed_form(policy, obs, act, adv, old_mean, old_log_std, clip,
 
 def aligned_flat_params(policy):
     """flat_params(policy) in a buffer whose mean-network part starts on a 16-byte boundary (the width-128 kernels read b1, W2, b2, W3 as
-    float4, and log_std -- 6 or 7 floats -- sits in front of them in the flat vector): pointers into it reach the kernels as they are."""
+    float4, and log_std -- 6, 7 or, for Cassie3d, 10 floats -- sits in front of them in the flat vector): pointers into it reach the kernels as they are."""
     theta = flat_params(policy)
     first = 0
     for nm, p in policy.named_parameters():
@@ -111,8 +111,9 @@ def aligned_flat_params(policy):
 
 class ClipGradKernels(Kernels):
     """The gradient of ppo_loss on minibatches of one batch, at the parameters in `theta` (a flat vector in parameter order that the caller
-    updates in place: aligned_flat_params): width 32 -> CassieTrpoClipGrad, width 128 -> CassiePgClipGrad, one launch each; CPU tensors,
-    other shapes, fused=False or a library without the symbols -> autograd of ppo_loss.  `kind`: "trpo_clip", "pg_clip" or "autograd"."""
+    updates in place: aligned_flat_params): width 32 -> CassieTrpoClipGrad, width 128 -> CassiePgClipGrad (Cassie3d's 45 x 10: CassiePg3dClipGrad), one
+    launch each; CPU tensors, other shapes, fused=False or a library without the symbols -> autograd of ppo_loss.  `kind`: "trpo_clip", "pg_clip",
+    "pg3d_clip" or "autograd"."""
 
     def __init__(self, policy, theta, obs, act, adv, old_mean, old_log_std, clip, entropy_coeff, fused=True):
         self.policy, self.theta, self.clip, self.entropy_coeff = policy, theta, float(clip), float(entropy_coeff)
@@ -123,11 +124,11 @@ class ClipGradKernels(Kernels):
         if not fused or lin is None or not obs.is_cuda or obs.dtype != torch.float32 or theta.dtype != torch.float32:
             return
         hs = hidden_sizes_of(policy)
-        prefix = {(32, 32): "CassieTrpo", (128, 128): "CassiePg"}.get(hs)
+        D, A, H = lin[0].in_features, lin[2].out_features, hs[0]
+        prefix = {(32, 32): "CassieTrpo", (128, 128): "CassiePg3d" if (D, A) == (45, 10) else "CassiePg"}.get(hs)   # (45 x 10: csrc/tu_pg3d.hip)
         if prefix is None or not available(prefix + "ClipGrad"):
             return
         super().__init__(obs.device, entry={k: prefix + k for k in ("ClipGrad", "ClipGradRows", "ParamCount")})
-        D, A, H = lin[0].in_features, lin[2].out_features, hs[0]
         NP = self.fn["ParamCount"](D, A)
         if NP == 0:
             return
@@ -156,7 +157,7 @@ class ClipGradKernels(Kernels):
             self.ent = torch.zeros(o, dtype=torch.float32, device=dev)
             self.ent[self.off["log_std"]:self.off["log_std"] + A] = -self.entropy_coeff
         self._bufs = {}
-        self.kind = "trpo_clip" if H == 32 else "pg_clip"
+        self.kind = {"CassieTrpo": "trpo_clip", "CassiePg": "pg_clip", "CassiePg3d": "pg3d_clip"}[prefix]
 
     def _rows(self, m):
         return self.fn["ClipGradRows"](m)
@@ -206,6 +207,7 @@ class PPO(FlatAdam, TRPO):
     """PPO on TRPO's sampler and baseline.  Switches (attributes, default True) that tests set to force the torch path: fused_policy_step,
     fused_gae (CassieTrpoGae), fused_grad (ClipGradKernels), fused_adam (CassiePgAdam).  last_grad_kind says which gradient ran."""
     ALGO = "ppo"
+    CASSIE3D = True   # make_cassie_ppo(..., env="cassie3d"): the 45 x 10 policy on csrc/tu_pg3d.hip and the baseline kernels at 45
 
     def __init__(self, env_step, env_reset, policy, baseline, n_envs, obs_dim, act_map, batch_size=10000, max_path_length=1000, discount=0.99,
                  learning_rate=3e-4, clip_range=0.2, gae_lambda=0.95, epochs=4, minibatch_size=None, entropy_coeff=0.0, beta1=0.9, beta2=0.999,
@@ -294,6 +296,7 @@ class PPO(FlatAdam, TRPO):
 
 def make_cassie_ppo(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, hidden_sizes=(128, 128), init_std=1.0, terrain=None,
                     sync_policy=True, **kw):
-    """PPO on the batched MI355X environment; the counterpart of vpg.make_cassie_vpg (same env, terrain and sync_policy rules)."""
+    """PPO on the batched MI355X environment; the counterpart of vpg.make_cassie_vpg (same env, terrain and sync_policy rules).  env="cassie3d"
+    (with control_mode and, through **kw, kp / kd) runs it on Cassie3dVecEnv: trpo.make_cassie_algo."""
     return make_cassie_algo(PPO, gaussian_policy_nets(hidden_sizes, init_std), broadcast_initial_policy, n_envs, kind, control_mode, device, trajectory, seed,
                             terrain, sync_policy, **kw)

@@ -668,8 +668,12 @@ class TRPO:
         if lin is None:
             return None
         D, A = lin[0].in_features, lin[2].out_features
-        entry = {(32, 32): "CassieTrpoPolicyStep", (128, 128): "CassiePgPolicyStep"}.get((lin[0].out_features, lin[1].out_features))
-        if (D, A) not in ((26, 6), (26, 7)) or entry is None or self.obs_dim != D or not available():
+        hs = (lin[0].out_features, lin[1].out_features)
+        if (D, A) == (45, 10):   # Cassie3d: the width-128 kernel of csrc/tu_pg3d.hip
+            entry = "CassiePg3dPolicyStep" if hs == (128, 128) else None
+        else:
+            entry = {(32, 32): "CassieTrpoPolicyStep", (128, 128): "CassiePgPolicyStep"}.get(hs) if (D, A) in ((26, 6), (26, 7)) else None
+        if entry is None or self.obs_dim != D or not available(entry):
             return None
         if not hasattr(self, "_env_actions") or self._env_actions.shape != (self.n_envs, A):
             self._env_actions = torch.empty((self.n_envs, A), dtype=torch.float64, device=dev)
@@ -954,13 +958,28 @@ class TRPO:
                   noise_step=int(self.noise_step), noise_seed=int(self.seed), gen_state=self.gen.get_state(), obs=None if self.obs is None else self.obs.cpu(),
                   path_t=self.path_t.cpu(), path_ret=self.path_ret.cpu(), steps_to_trunc=int(self._steps_to_trunc),
                   env_state=None if env is None or not hasattr(env, "get_full_state_host") else torch.from_numpy(env.get_full_state_host()),
-                  terrain=terrain_lib.spec_key(getattr(self, "terrain_spec", None)))
+                  terrain=terrain_lib.spec_key(getattr(self, "terrain_spec", None)), **self._env_family_fields())
         ck.update(self._snapshot_fields())
         mine = self._rank_path(path)
         torch.save(ck, mine + ".tmp")
         os.replace(mine + ".tmp", mine)
 
     ALGO = "trpo"   # the snapshot's "algo" entry (a plain TRPO snapshot has none)
+    CASSIE3D = False   # whether make_cassie_algo builds this algorithm on Cassie3d (env="cassie3d"): PPO
+
+    def _env_family_fields(self):
+        """The environment family of the run -- "cassie2d" (also: no make_cassie_algo, as the CPU tests' toy environments) or "cassie3d", then
+        with what Cassie3dVecEnv was configured with (make_cassie_algo sets env_family / env_config)."""
+        return dict(env_family=getattr(self, "env_family", "cassie2d"), env_config=getattr(self, "env_config", None))
+
+    def _check_env_family(self, ck):
+        """A snapshot continues on the family (and, for Cassie3d, the control mode and gains) it was written on; one written before the
+        entry existed is Cassie2d's."""
+        name, mine, theirs = type(self).__name__, self._env_family_fields(), dict(env_family=ck.get("env_family", "cassie2d"), env_config=ck.get("env_config"))
+        if theirs["env_family"] != mine["env_family"]:
+            raise ValueError("%s.load: the snapshot was written on %s, this run is on %s" % (name, theirs["env_family"], mine["env_family"]))
+        if theirs["env_config"] != mine["env_config"]:
+            raise ValueError("%s.load: the snapshot's %s was configured with %r, this run's with %r" % (name, mine["env_family"], theirs["env_config"], mine["env_config"]))
 
     @property
     def hidden_sizes(self):
@@ -992,6 +1011,7 @@ class TRPO:
         mine = self._rank_path(path)
         ck = torch.load(mine if os.path.exists(mine) else path, map_location="cpu", weights_only=True)
         self._load_fields(ck)
+        self._check_env_family(ck)
         # the ground is part of the run: resuming on other terrain would silently be a different run (snapshots without the key: flat floor)
         mine_spec, theirs = terrain_lib.spec_key(getattr(self, "terrain_spec", None)), ck.get("terrain")
         if mine_spec != theirs:
@@ -1007,7 +1027,7 @@ class TRPO:
         # noise counter existed have no "noise_step": policy / baseline only, restored = False)
         complete = all(k in ck for k in ("noise_step", "obs", "path_t", "path_ret")) and ck.get("n_envs_global", n_global) == n_global
         if restore_sampler and complete and os.path.exists(mine) and ck.get("env_state") is not None and env is not None \
-                and tuple(ck["env_state"].shape) == (self.n_envs, 88):
+                and tuple(ck["env_state"].shape) == (self.n_envs, getattr(env, "FULL_STATE_WIDTH", 88)):   # (88: the Cassie2d record)
             env.set_full_state_host(ck["env_state"].numpy())
             self.noise_step, self.seed = ck["noise_step"], ck.get("noise_seed", self.seed)
             if ck.get("gen_state") is not None:
@@ -1029,24 +1049,44 @@ def broadcast_initial_policy(algo):
 
 
 def make_cassie_algo(cls, make_nets, broadcast, n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, terrain=None, sync_policy=True,
-                     terrain_ids=None, **kw):
-    """cls on the batched MI355X environment: what every make_cassie_* is.  make_nets(obs_dim, act_dim, dev) -> the constructor's arguments between
+                     terrain_ids=None, env="cassie2d", kp=10.0, kd=5.0, **kw):
+    """cls on the batched MI355X environment: what every make_cassie_* is.  env: the environment family -- "cassie2d" (CassieVecEnv: kind, trajectory,
+    terrain) or "cassie3d" (Cassie3dVecEnv(n_envs, control_mode, kp, kd): standing reset, 45 observations, 10 actions; no terrain, gait or kind, and
+    only for an algorithm with CASSIE3D set -- PPO; the others refuse rather than run untested on their torch paths).  make_nets(obs_dim, act_dim, dev) -> the constructor's arguments between
     env_reset and n_envs (the policy first), built right after torch.manual_seed(seed): every rank builds the same initial networks, and with
     sync_policy `broadcast(algo)` makes rank 0's authoritative anyway.  sync_policy=False: NOTHING collective happens in here (the env, its
     workspaces, the networks are local allocations that can fail on one rank alone); the caller agrees on success across ranks first and then
     broadcasts (bench.py's TRPO stage).  terrain: None (the flat floor) or a spec of terrain.terrain_spec -- every environment on its own field of
     the spec's library, drawn by terrain.assign_terrains over terrain_ids(the GLOBAL env ids) (default: the ids themselves); snapshots record it."""
-    from .vec_env import CassieVecEnv
-    env = CassieVecEnv(n_envs, kind=kind, control_mode=control_mode, n_substeps=10, auto_reset=True, device=device, trajectory=trajectory)
+    if env not in ("cassie2d", "cassie3d"):
+        raise ValueError("make_cassie_algo: env must be 'cassie2d' or 'cassie3d', got %r" % (env,))
+    family, env_config = env, None
+    if family == "cassie3d":   # (checked before any device is touched)
+        if not cls.CASSIE3D:
+            raise ValueError("%s does not run on env='cassie3d': PPO (ppo.make_cassie_ppo) is the algorithm built for the 45 x 10 policy" % cls.__name__)
+        if terrain is not None or trajectory is not None or kind != "walk":
+            raise ValueError("env='cassie3d' has no terrain, reference gait or kind (got terrain=%r, trajectory %s, kind=%r): it is the standing-reset Cassie3d"
+                             % (terrain, "given" if trajectory is not None else "None", kind))
+        if control_mode not in ("PD", "Torque"):
+            raise ValueError("env='cassie3d' has the control modes 'PD' and 'Torque', not %r" % (control_mode,))
+        import numpy as np
+        from .vec_env3d import NU, Cassie3dVecEnv
+        env_config = dict(control_mode=control_mode, kp=np.broadcast_to(np.asarray(kp, dtype=np.float64), (NU,)).tolist(),
+                          kd=np.broadcast_to(np.asarray(kd, dtype=np.float64), (NU,)).tolist())
+        env = Cassie3dVecEnv(n_envs, control_mode=control_mode, n_substeps=10, auto_reset=True, kp=kp, kd=kd, device=device)
+    else:
+        from .vec_env import CassieVecEnv
+        env = CassieVecEnv(n_envs, kind=kind, control_mode=control_mode, n_substeps=10, auto_reset=True, device=device, trajectory=trajectory)
     env.use_torch_stream()
     dev = "cuda:%d" % device
     bufs = env.alloc()
     torch.manual_seed(seed)  # trpo_cassie.py:53 seed=1
     obs_w = env.observation_space.shape[0]  # what step() emits (26 for both kinds); the networks are sized from the env, as trpo_cassie.py does through env.spec
-    nets = make_nets(obs_w, env.adim, dev)
+    nets = make_nets(obs_w, env.adim if family == "cassie2d" else len(env.action_space.low), dev)
     act_map = NormalizedActions(env.action_space.low, env.action_space.high, dev)
     algo = cls(lambda a: env.step(a, bufs), lambda: env.reset(bufs), *nets, n_envs, obs_w, act_map, seed=seed, env_reset_masked=lambda m: env.reset(bufs, mask=m), **kw)
     algo.env = env
+    algo.env_family, algo.env_config = family, env_config
     algo.terrain_spec = terrain
     if terrain is not None:
         ids = algo.env_ids if terrain_ids is None else terrain_ids(algo.env_ids)

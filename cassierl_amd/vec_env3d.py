@@ -132,6 +132,15 @@ class Cassie3dVecEnv(Cassie3dVec):
             self.close()
             raise ValueError("Cassie3dVecEnvConfigure failed (%d): %s" % (rc, msg))
 
+    # the snapshot hooks of the learning code (trpo.TRPO.save / load): the whole record of every environment
+    FULL_STATE_WIDTH = STATE_STRIDE
+
+    def get_full_state_host(self):
+        return self.get_state_host()
+
+    def set_full_state_host(self, s):
+        self.set_state_host(s)
+
     @property
     def observation_space(self):
         from .vec_env import Box

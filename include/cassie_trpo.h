@@ -92,7 +92,7 @@ int CassieTrpoReturnsAdvantages(const float* obs_dev, const long long* t_dev, co
 /* Normal equations of the baseline's ridge regression: Z'Z for Z = [features | y] (m samples, 2 obs_dim + 5 columns padded to a multiple
  * of 16) on the FP64 matrix cores.  partial [CassieTrpoGramRows()][CassieTrpoGramRowSize(obs_dim)]: per wavefront the UPPER 16 x 16 blocks
  * (r <= c, r-major) of the Gram matrix, each row-major; the caller adds the rows up: X'X = Z'Z[:features, :features], X'y = Z'Z[:features, features]. */
-/* (A + reg I) x = b, A [F][F] symmetric positive semi-definite (F = CassieTrpoBaselineFeatures(obs_dim): 56 or 38), by Cholesky on the device; a failed factorisation or a non-finite
+/* (A + reg I) x = b, A [F][F] symmetric positive semi-definite (F = CassieTrpoBaselineFeatures(obs_dim): 56, 38 or -- obs_dim 45 -- 94), by Cholesky on the device; a failed factorisation or a non-finite
  * solution retries with ten times the regulariser, five times in all (LinearFeatureBaseline.fit's rule, without a host read-back). */
 int CassieTrpoRidgeSolve(const double* A_dev, const double* b_dev, int F, double reg, double* x_dev, void* stream);
 int CassieTrpoGramRows(void);
@@ -293,6 +293,20 @@ int CassiePgClipGrad(const float* obs_dev, int n, int obs_dim, int act_dim, cons
                      const float* W3, const float* b3, const long long* idx_dev, int m, const float* act_dev, const float* adv_dev,
                      const float* old_mean_dev, const float* log_std_old, const float* log_std_new, float clip, float scale, float* partial_dev,
                      double* stats_dev, void* stream);
+
+/* ---- width-128 policy at 45 x 10: PPO on Cassie3d (cassierl_amd/ppo.py with env="cassie3d", csrc/tu_pg3d.hip).  The contracts of
+ * CassiePgParamCount, CassiePgPolicyStep, CassiePgClipGradRows and CassiePgClipGrad for the one shape obs_dim = 45, act_dim = 10 (any other:
+ * 0 / CASSIE_EINVAL); Adam is CassiePgAdam.  The baseline kernels above take obs_dim = 45 (94 features) under their own names. */
+int CassiePg3dParamCount(int obs_dim, int act_dim);
+int CassiePg3dPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2,
+                         const float* b2, const float* W3, const float* b3, const float* log_std, const float* noise_dev,
+                         const double* low_dev, const double* high_dev, float* obs32_dev, float* mean_dev, float* act_dev,
+                         double* env_actions_dev, void* stream);
+int CassiePg3dClipGradRows(int m);
+int CassiePg3dClipGrad(const float* obs_dev, int n, int obs_dim, int act_dim, const float* W1, const float* b1, const float* W2, const float* b2,
+                       const float* W3, const float* b3, const long long* idx_dev, int m, const float* act_dev, const float* adv_dev,
+                       const float* old_mean_dev, const float* log_std_old, const float* log_std_new, float clip, float scale, float* partial_dev,
+                       double* stats_dev, void* stream);
 
 /* ---- ES (cassierl_amd/es.py, csrc/tu_es.hip): antithetic perturbations of the 32 x 32 tanh mean network drawn from a shared noise table.
  * theta [P] is the mean network's parameter row [W1 | b1 | W2 | b2 | W3 | b3] (row-major as torch.nn.Linear), P = CassieEsParamCount; table

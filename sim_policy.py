@@ -43,8 +43,13 @@ def main():
                                terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (32, 32))))
     elif ck.get("algo") == "ppo":   # a train_ppo.py snapshot: the policy's shape comes from it; only the policy is loaded, so the batch shape is free
         from cassierl_amd.ppo import make_cassie_ppo
-        algo = make_cassie_ppo(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
-                               terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (128, 128))), batch_size=args.envs, minibatch_size=args.envs)
+        if ck.get("env_family", "cassie2d") == "cassie3d":   # written by train_ppo.py --env cassie3d: the control mode and gains are the snapshot's
+            cfg = ck["env_config"]
+            env_kw = dict(env="cassie3d", control_mode=cfg["control_mode"], kp=cfg["kp"], kd=cfg["kd"])
+        else:
+            env_kw = dict(kind=args.kind, control_mode=args.control_mode, trajectory=default_gait(), terrain=terrain)
+        algo = make_cassie_ppo(args.envs, device=0, seed=args.seed, hidden_sizes=tuple(ck.get("hidden_sizes", (128, 128))), batch_size=args.envs,
+                               minibatch_size=args.envs, **env_kw)
     elif ck.get("algo") == "es":   # a train_es.py snapshot: the unperturbed parameters, rolled out with the mean (the noise table is the snapshot's)
         from cassierl_amd.es import make_cassie_es
         if args.envs % 2:

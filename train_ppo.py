@@ -22,8 +22,11 @@ def main():
     ap.add_argument("--envs-per-gpu", type=int, default=4096)
     ap.add_argument("--horizon", type=int, default=4, help="Env.steps per environment per iteration")
     ap.add_argument("--n-itr", type=int, default=10)
+    ap.add_argument("--env", default="cassie2d", choices=["cassie2d", "cassie3d"], help="cassie3d: the 3-D robot from its standing reset (45 observations, 10 actions)")
     ap.add_argument("--kind", default="walk", choices=["walk", "stand"])
     ap.add_argument("--control-mode", default="PD", choices=["PD", "Torque", "OSC"])
+    ap.add_argument("--kp", type=float, default=10.0, help="--env cassie3d, PD mode: proportional gain of the ten actuated hinges")
+    ap.add_argument("--kd", type=float, default=5.0, help="--env cassie3d, PD mode: damping gain")
     ap.add_argument("--snapshot", default="")
     ap.add_argument("--load-policy", default="")
     ap.add_argument("--timing", action="store_true", help="report rollout / update seconds separately (adds synchronisations)")
@@ -49,14 +52,15 @@ def main():
     rank, local_rank, world = R.init_distributed()
     dev = R.local_device(local_rank) if world > 1 else 0   # CASSIE_DEVICE_MAP (test hook): several ranks on one GPU
     torch.cuda.set_device(dev)
-    traj = default_gait()
     from cassierl_amd.terrain import terrain_spec
     terrain = terrain_spec(args.terrain_dir, args.num_terrains, args.terrain_elevation, args.terrain_seed) if args.terrain_dir else None
     hidden = tuple(int(x) for x in args.hidden.split(","))
-    algo = make_cassie_ppo(args.envs_per_gpu, kind=args.kind, control_mode=args.control_mode, device=dev, trajectory=traj, seed=1,
+    # the environment: Cassie2d with its gait, or Cassie3d with its gains (which has neither gait nor kind: make_cassie_algo refuses them)
+    env_kw = dict(trajectory=default_gait()) if args.env == "cassie2d" else dict(env="cassie3d", kp=args.kp, kd=args.kd)
+    algo = make_cassie_ppo(args.envs_per_gpu, kind=args.kind, control_mode=args.control_mode, device=dev, seed=1,
                            hidden_sizes=hidden, init_std=args.init_std, learning_rate=args.learning_rate, clip_range=args.clip_range,
                            gae_lambda=args.gae_lambda, epochs=args.epochs, minibatch_size=args.minibatch_size or None, entropy_coeff=args.entropy_coeff,
-                           batch_size=args.envs_per_gpu * world * args.horizon, terrain=terrain)
+                           batch_size=args.envs_per_gpu * world * args.horizon, terrain=terrain, **env_kw)
     algo.timing = args.timing
     if args.torch_update:
         algo.fused_grad = algo.fused_adam = algo.fused_gae = False
