@@ -19,7 +19,7 @@ would disagree with this paragraph, this paragraph is the contract of this modul
     run, each on batch_size transitions drawn uniformly with replacement;
   * one update: y = r + (1 - terminal) discount Q'(s', mu'(s'));  critic loss mean((Q(s, a) - y)^2), one Adam step at qf_learning_rate;  actor
     loss -mean(Q(s, mu(s))) with the critic AFTER its step, one Adam step at policy_learning_rate;  target <- (1 - tau) target + tau live for
-    both networks, tau = 0.001.  Adam is Lasagne's (vpg.adam_step_), each network with its own m, v, t.  No weight decay; replay_pool_size
+    both networks, tau = 0.001.  Adam is Lasagne's (adam.adam_step_), each network with its own m, v, t.  No weight decay; replay_pool_size
     1 000 000.
 
 With N environments: the rules of every algorithm on the replay pool, offpolicy.py, "With N environments" (rule 6: the OU noise's normals).
@@ -35,9 +35,9 @@ import math
 import torch
 from torch import nn
 
-from .offpolicy import OffPolicy, PoolKernels, ReplayPool, _F, _NoBaseline, _P, _adam_on, _ptrs, broadcast_initial_networks, default_pool_size, \
+from .comm import all_mean_
+from .offpolicy import OffPolicy, PoolKernels, ReplayPool, _F, _P, _adam_on, _ptrs, broadcast_initial_networks, default_pool_size, \
     make_cassie_offpolicy, new_adam, soft_update_   # the moved names stay reachable as ddpg.<name> (tools, tests)
-from .trpo import all_mean_
 
 ACTOR, CRITIC = 0, 1   # CASSIE_DDPG_ACTOR / CASSIE_DDPG_CRITIC
 

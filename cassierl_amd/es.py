@@ -4,7 +4,7 @@ for a whole episode, nothing is stored per step, and the update is one weighted 
 There is no reference counterpart (rllab ships the family as CEM / CMA-ES and no script of the reference uses it): the torch statements in this
 module are the specification, the kernels of csrc/tu_es.hip (and, for the 128 x 128 policy's step, csrc/tu_es_wide.hip) evaluate them.
 
-  parameters  theta = flat_params(policy.mean_net), the row [W1 | b1 | W2 | b2 | W3 | b3] (vpg._MEAN_ORDER, the actor row of csrc/mlp32_tiles.h),
+  parameters  theta = flat_params(policy.mean_net), the row [W1 | b1 | W2 | b2 | W3 | b3] (policy._MEAN_ORDER, the actor row of csrc/mlp32_tiles.h),
               P entries: 2118 for the shape (26, 6), 2151 for (26, 7), 1863 for (17, 7) at 32 x 32 hidden units; 20 742, 20 871 and 19 719 at
               128 x 128 (19 590 for (17, 6)).  log_std is never touched, so a TRPO run can load an ES snapshot and continue from it.
   noise       table = randn(table_size) float32 on the device from a generator seeded by table_seed (default 1 << 24 entries, 64 MB): regenerated
@@ -23,10 +23,10 @@ module are the specification, the kernels of csrc/tu_es.hip (and, for the 128 x 
   update      all fitness values gathered (rollout.gather_returns) and shaped -- centered ranks in [-0.5, 0.5] over all 2 M_global values
               (argsort(stable=True): ties by position), or fitness_shaping="zscore" --, per direction w_d = u(2d) - u(2d + 1),
                 g = (1 / (2 M_global sigma)) sum_d w_d eps_d   (es_grad_torch; CassieEsGrad: each rank sums its shard, then all_sum_),
-              descent direction -g + l2_coeff theta, one Lasagne Adam step (vpg.adam_step_ / CassiePgAdam).
+              descent direction -g + l2_coeff theta, one Lasagne Adam step (adam.adam_step_ / CassiePgAdam).
 
-Defaults are OpenAI's: sigma 0.02, learning_rate 0.01, l2_coeff 0.005; max_path_length 1000.  The snapshot machinery and the gather are TRPO's
-(cassierl_amd/trpo.py), unchanged.  The 32 x 32 and the 128 x 128 policy in float32 on the GPU have kernels (the policy step is one kernel per width;
+Defaults are OpenAI's: sigma 0.02, learning_rate 0.01, l2_coeff 0.005; max_path_length 1000.  The snapshot machinery and the gather are sampler.Sampler's,
+shared with every other algorithm.  The 32 x 32 and the 128 x 128 policy in float32 on the GPU have kernels (the policy step is one kernel per width;
 the bookkeeping, the gradient and Adam do not see the width); other hidden sizes, CPU tensors, float64 or a library without the symbols -- one
 without the CassieEsWide* symbols at width 128 only -- take the torch statements.
 """
@@ -36,8 +36,10 @@ import time
 import torch
 
 from ._lib import Kernels, available, ptr
-from .trpo import (TRPO, FlatAdam, NormalizedActions, _two_layer_tanh, _world, all_sum_, broadcast_initial_policy, flat_params, gaussian_policy_nets,
-                   make_cassie_algo, set_flat_params)
+from .adam import FlatAdam
+from .comm import _world, all_sum_
+from .policy import NormalizedActions, _two_layer_tanh, flat_params, set_flat_params
+from .sampler import Sampler, broadcast_initial_policy, gaussian_policy_nets, make_cassie_algo
 
 
 # --------------------------------------------------------------------------------------------- the torch statements
@@ -224,8 +226,8 @@ def make_table(size, seed, device):
 
 
 # --------------------------------------------------------------------------------------------- ES
-class ES(FlatAdam, TRPO):
-    """ES on TRPO's snapshot machinery and gather; the baseline is unused.  Switches (attributes, default True) that tests set to force the torch
+class ES(FlatAdam, Sampler):
+    """ES on Sampler's snapshot machinery and gather; the baseline the constructor takes (the on-policy family's signature) is unused.  Switches (attributes, default True) that tests set to force the torch
     statements: fused_policy_step (CassieEsPolicyStep), fused_book (CassieEsBook), fused_grad (CassieEsGrad), fused_adam (CassiePgAdam).
     last_policy_step_kind ("es_step" / "es_wide_step" at width 128 / "torch"), last_book_fused, last_grad_kind ("es_grad" / "torch") and last_adam_fused say what ran."""
     ALGO = "es"
@@ -235,8 +237,9 @@ class ES(FlatAdam, TRPO):
                  env_id0=None):
         if n_envs <= 0 or n_envs % 2:
             raise ValueError("ES: n_envs must be positive and even (two environments per direction), got %d" % n_envs)
-        super().__init__(env_step, env_reset, policy, baseline, n_envs, obs_dim, act_map, batch_size=n_envs * _world(), max_path_length=max_path_length, seed=seed,
+        super().__init__(env_step, env_reset, policy, n_envs, obs_dim, act_map, batch_size=n_envs * _world(), max_path_length=max_path_length, seed=seed,
                          env_reset_masked=env_reset_masked, env_id0=env_id0)
+        self.baseline = baseline   # (never fitted, never written: the snapshot's "baseline" entry is None)
         if self.env_id0 % 2:
             raise ValueError("ES: a shard must start on an even environment id, got %d" % self.env_id0)
         shape_fitness(torch.zeros(2), fitness_shaping)
@@ -363,7 +366,7 @@ class ES(FlatAdam, TRPO):
         self.itr += 1
         return stats
 
-    # ---- snapshot: TRPO's, plus the algorithm, the policy shape, the hyper-parameters, the Adam state, the table's seed and size (never the
+    # ---- snapshot: Sampler's, plus the algorithm, the policy shape, the hyper-parameters, the Adam state, the table's seed and size (never the
     # table) and the offset generator
     def _snapshot_fields(self):
         return dict(super()._snapshot_fields(), sigma=self.sigma, learning_rate=self.learning_rate, l2_coeff=self.l2_coeff, fitness_shaping=self.fitness_shaping,

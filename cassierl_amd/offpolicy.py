@@ -28,7 +28,10 @@ import torch
 import torch.distributed as dist
 
 from ._lib import Kernels, available, ptr as _P
-from .trpo import TRPO, NormalizedActions, _world, adam_step_, all_mean_, all_sum_, flat_params, make_cassie_algo, set_flat_params
+from .adam import adam_step_
+from .comm import _world, all_mean_, all_sum_
+from .policy import NormalizedActions, flat_params, set_flat_params
+from .sampler import Sampler, make_cassie_algo
 
 
 class ReplayPool:
@@ -103,10 +106,6 @@ def _F(*xs):
     return [ct.c_float(x) for x in xs]
 
 
-class _NoBaseline:
-    coeffs = None
-
-
 class PoolKernels(Kernels):
     """Base of DdpgKernels, SacKernels and Td3Kernels: the library calls of one update on the networks' own storage (_lib.Kernels: ENTRY, `fn`,
     _call; the call sites pass the stream themselves, where the kernel takes one)."""
@@ -139,10 +138,10 @@ class PoolKernels(Kernels):
         return part
 
 
-class OffPolicy(TRPO):
-    """An algorithm on the replay pool, on TRPO's sampler state (path clocks, exploration-noise generator, truncation, snapshot).  Switches
+class OffPolicy(Sampler):
+    """An algorithm on the replay pool, on Sampler's state (path clocks, exploration-noise generator, truncation, snapshot).  Switches
     (attributes, default True) that tests set to force the torch statements: fused_policy_step (the policy-step kernel + CassieDdpgPoolCommit),
-    fused_update (the update launches), fused_sampler_step (TRPO's).  last_update_kind says which update ran.  A subclass supplies the class
+    fused_update (the update launches), fused_sampler_step (Sampler's).  last_update_kind says which update ran.  A subclass supplies the class
     attributes and hooks below, _explore, update and its own constructor arguments ("Off-policy family")."""
 
     ALGO = None         # the snapshot's "algo" entry
@@ -157,7 +156,7 @@ class OffPolicy(TRPO):
                  snapshot_pool):
         """The live networks besides the policy are attributes already (NETS names them).  Sets up the targets, this rank's share of the batch, the
         schedule, the pool, the index generator's seeding and the per-iteration accumulators."""
-        super().__init__(env_step, env_reset, policy, _NoBaseline(), n_envs, obs_dim, act_map, batch_size=batch_size, max_path_length=max_path_length,
+        super().__init__(env_step, env_reset, policy, n_envs, obs_dim, act_map, batch_size=batch_size, max_path_length=max_path_length,
                          discount=discount, seed=seed, env_reset_masked=env_reset_masked, env_id0=env_id0)
         for live, target in self.NETS:
             if target is not None:
@@ -352,7 +351,7 @@ class OffPolicy(TRPO):
         self.itr += 1
         return out
 
-    # ---- snapshot: TRPO's (actor under "policy", sampler state, env records) plus everything else a resumed run needs to BE the interrupted run
+    # ---- snapshot: Sampler's (actor under "policy", sampler state, env records) plus everything else a resumed run needs to BE the interrupted run
     def _saved_nets(self):
         return [name for pair in self.NETS for name in pair if name not in (None, "policy")]
 
@@ -378,7 +377,7 @@ class OffPolicy(TRPO):
         self._pending = ck
 
     def load(self, path, restore_sampler=True):
-        """TRPO.load, then -- only where the sampler came back, i.e. this IS the interrupted run -- the index generator, _load_sampler_extra and the
+        """Sampler.load, then -- only where the sampler came back, i.e. this IS the interrupted run -- the index generator, _load_sampler_extra and the
         pool.  A snapshot written without its pool (snapshot_pool=False) restarts with an empty one; `pool_restored` says which."""
         extra, restored = super().load(path, restore_sampler)
         ck, self._pending = self._pending, None
@@ -415,7 +414,7 @@ def broadcast_initial_networks(algo):
 
 def make_cassie_offpolicy(cls, make_nets, n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, terrain=None, sync_policy=True,
                           replay_pool_size=None, **kw):
-    """cls on the batched MI355X environment (trpo.make_cassie_algo: env, terrain and sync_policy rules).  make_nets(obs_dim, act_dim) -> the networks
+    """cls on the batched MI355X environment (sampler.make_cassie_algo: env, terrain and sync_policy rules).  make_nets(obs_dim, act_dim) -> the networks
     of cls's constructor, the policy first, built after torch.manual_seed(seed).  replay_pool_size: rows of this rank's pool (default: rllab's
     1 000 000 rounded up to a multiple of n_envs; a row is 4 (2 D + A + 2) bytes)."""
     return make_cassie_algo(cls, lambda D, A, dev: [net.to(dev) for net in make_nets(D, A)], broadcast_initial_networks, n_envs, kind, control_mode, device,

@@ -6,18 +6,18 @@ statements in this module are the specification, the kernels of csrc/tu_ppo.hip 
   advantages  per environment column of the [T][N] batch, backwards, float64 (gae_advantages; CassieTrpoGae):
                 live = 1 - cut;  delta = r + gamma live V(s') - V(s);  adv = delta + gamma lambda live adv';  returns as TRPO's.
               V is the LinearFeatureBaseline; a path cut at max_path_length is terminal, as for TRPO and VPG.  Centring and the baseline
-              fit are TRPO.process's.
+              fit are OnPolicy.process's.
   loss        of one minibatch of M samples (all ranks together), ratio = exp(ll_new(a) - ll_old(a))  (ppo_loss):
                 L = -(1/M) sum min(ratio adv, clip(ratio, 1 - eps, 1 + eps) adv) - entropy_coeff sum_a (log_std_a + 0.5 log(2 pi e))
   gradient    in closed form (clipped_grad_closed_form; CassieTrpoClipGrad / CassiePgClipGrad evaluate it in one launch):
                 clipped = (adv > 0 and ratio > 1 + eps) or (adv < 0 and ratio < 1 - eps);  w = clipped ? 0 : ratio adv;  z = (a - mean) / std
                 dL/dmean = -(1/M) w z / std;   dL/dlog_std = -(1/M) sum_s w (z^2 - 1) - entropy_coeff
   update      `epochs` passes over the rollout; per pass a fresh device permutation, minibatch j = rows perm[j m : (j + 1) m] with
-              m = minibatch_size / world; per minibatch: gradient -> mean over ranks -> one Lasagne Adam step (vpg.adam_step_ / CassiePgAdam),
+              m = minibatch_size / world; per minibatch: gradient -> mean over ranks -> one Lasagne Adam step (adam.adam_step_ / CassiePgAdam),
               the Adam state kept across minibatches and iterations.  Nothing is read back inside the loop.  As for DDPG, the result depends
               on the number of ranks unless minibatch_size equals the batch (each rank permutes its own shard).
 
-The sampler, exploration noise, baseline kernels and snapshot machinery are TRPO's (cassierl_amd/trpo.py), unchanged.
+The sampler, exploration noise, baseline kernels and snapshot machinery are sampler.OnPolicy's, shared with TRPO and VPG.
 """
 import ctypes as ct
 import math
@@ -26,8 +26,11 @@ import torch
 import torch.distributed as dist
 
 from ._lib import Kernels, available, ptr
-from .trpo import (TRPO, AnalyticFisher, FlatAdam, GaussianMLPPolicy, _MEAN_ORDER, _two_layer_tanh, _world, add_to_log_std_slot_, all_mean_, all_sum_,
-                   broadcast_initial_policy, flat_grad, flat_params, gaussian_policy_nets, hidden_sizes_of, make_cassie_algo, set_flat_params)
+from .adam import FlatAdam
+from .comm import _world, all_mean_, all_sum_
+from .fisher import AnalyticFisher
+from .policy import GaussianMLPPolicy, _MEAN_ORDER, _two_layer_tanh, add_to_log_std_slot_, flat_grad, flat_params, hidden_sizes_of, set_flat_params
+from .sampler import OnPolicy, broadcast_initial_policy, gaussian_policy_nets, make_cassie_algo
 
 
 # --------------------------------------------------------------------------------------------- the torch statements
@@ -203,8 +206,8 @@ class ClipGradKernels(Kernels):
 
 
 # --------------------------------------------------------------------------------------------- PPO
-class PPO(FlatAdam, TRPO):
-    """PPO on TRPO's sampler and baseline.  Switches (attributes, default True) that tests set to force the torch path: fused_policy_step,
+class PPO(FlatAdam, OnPolicy):
+    """PPO on OnPolicy's sampler and baseline.  Switches (attributes, default True) that tests set to force the torch path: fused_policy_step,
     fused_gae (CassieTrpoGae), fused_grad (ClipGradKernels), fused_adam (CassiePgAdam).  last_grad_kind says which gradient ran."""
     ALGO = "ppo"
     CASSIE3D = True   # make_cassie_ppo(..., env="cassie3d"): the 45 x 10 policy on csrc/tu_pg3d.hip and the baseline kernels at 45
@@ -236,7 +239,7 @@ class PPO(FlatAdam, TRPO):
         return m
 
     def _advantages(self, bk, batch, obs, tt):
-        """TRPO.process's hook with GAE(lambda) advantages: CassieTrpoGae, or gae_advantages on the values of the kernels or of the baseline."""
+        """OnPolicy.process's hook with GAE(lambda) advantages: CassieTrpoGae, or gae_advantages on the values of the kernels or of the baseline."""
         T, N = batch["rew"].shape
         coeffs = self.baseline.coeffs
         self.last_gae_fused = bk is not None and getattr(self, "fused_gae", True)
@@ -281,7 +284,7 @@ class PPO(FlatAdam, TRPO):
         return dict(loss_first=rows[0][0] / M - ent, loss_last=rows[-1][0] / M - ent, mean_kl=sum(r[1] for r in rows) / (M * len(rows)),
                     clip_frac=sum(r[2] for r in rows) / (M * len(rows)), grad_norm=sum(r[3] for r in rows) / len(rows), minibatch_steps=len(rows))
 
-    # ---- snapshot: TRPO's, plus the algorithm, the policy shape, the hyper-parameters, the Adam state and the permutation generator
+    # ---- snapshot: Sampler's, plus the algorithm, the policy shape, the hyper-parameters, the Adam state and the permutation generator
     def _snapshot_fields(self):
         return dict(super()._snapshot_fields(), learning_rate=float(self.learning_rate), clip_range=float(self.clip_range), gae_lambda=float(self.gae_lambda),
                     epochs=int(self.epochs), minibatch_size=int(self.minibatch_size), entropy_coeff=float(self.entropy_coeff), **self._adam_snapshot(),
@@ -297,6 +300,6 @@ class PPO(FlatAdam, TRPO):
 def make_cassie_ppo(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, hidden_sizes=(128, 128), init_std=1.0, terrain=None,
                     sync_policy=True, **kw):
     """PPO on the batched MI355X environment; the counterpart of vpg.make_cassie_vpg (same env, terrain and sync_policy rules).  env="cassie3d"
-    (with control_mode and, through **kw, kp / kd) runs it on Cassie3dVecEnv: trpo.make_cassie_algo."""
+    (with control_mode and, through **kw, kp / kd) runs it on Cassie3dVecEnv: sampler.make_cassie_algo."""
     return make_cassie_algo(PPO, gaussian_policy_nets(hidden_sizes, init_std), broadcast_initial_policy, n_envs, kind, control_mode, device, trajectory, seed,
                             terrain, sync_policy, **kw)

@@ -18,7 +18,7 @@ this paragraph, this paragraph wins]:
          moved); one Adam step at alpha_learning_rate; target_entropy defaults to -A.  The alpha of steps 1 and 3 is the value from before
          this update.  fixed_alpha=<float> sets alpha to that value and switches step 4 off;
       5. both target critics: target <- (1 - tau) target + tau live.
-    Adam is vpg.adam_step_; every gradient, log_alpha's included, is averaged over ranks before its Adam step.
+    Adam is adam.adam_step_; every gradient, log_alpha's included, is averaged over ranks before its Adam step.
 
 With N environments it is the off-policy base (offpolicy.py, "With N environments", rules 1-5 and 7; truncation keeps the true s' with terminal = 0;
 the same train_step / train_iteration / updates_per_step, one read-back per epoch).  What differs from DDPG:
@@ -42,10 +42,10 @@ import torch.distributed as dist
 from torch import nn
 from torch.nn import functional as F
 
+from .adam import adam_step_
+from .comm import all_mean_
 from .ddpg import CRITIC, ContinuousMLPQFunction, _init_hidden, _init_output
 from .offpolicy import OffPolicy, PoolKernels, _F, _P, _adam_on, _ptrs, broadcast_initial_networks, make_cassie_offpolicy, new_adam, soft_update_
-from .trpo import all_mean_
-from .vpg import adam_step_
 
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
 

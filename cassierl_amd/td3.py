@@ -12,7 +12,7 @@ source is on this machine.  Where a published implementation would disagree with
          -mean(Q1(s, mu(s))) through qf1 AFTER its step, one Adam step at policy_learning_rate; then all three targets
          target <- (1 - tau) target + tau live.  On every other update the actor and ALL targets stay as they are: the critics regress towards
          targets that stand still between two actor steps, which is what the delay is for.
-    Adam is vpg.adam_step_; every gradient is averaged over ranks before its Adam step.
+    Adam is adam.adam_step_; every gradient is averaged over ranks before its Adam step.
 
 With N environments it is the off-policy base (offpolicy.py, "With N environments", rules 1-5 and 7; truncation keeps the true s' with terminal = 0;
 the same train_step / train_iteration / updates_per_step, one read-back per epoch).  What differs from DDPG:
@@ -32,9 +32,9 @@ import ctypes as ct
 
 import torch
 
+from .comm import all_mean_
 from .ddpg import ACTOR, CRITIC, ContinuousMLPQFunction, DdpgKernels, DeterministicMLPPolicy, kernels_cover as ddpg_kernels_cover
 from .offpolicy import OffPolicy, PoolKernels, _F, _P, _adam_on, _ptrs, broadcast_initial_networks, make_cassie_offpolicy, new_adam, soft_update_
-from .trpo import all_mean_
 
 
 def delayed(n_updates, policy_delay):

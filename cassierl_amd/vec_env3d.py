@@ -132,7 +132,7 @@ class Cassie3dVecEnv(Cassie3dVec):
             self.close()
             raise ValueError("Cassie3dVecEnvConfigure failed (%d): %s" % (rc, msg))
 
-    # the snapshot hooks of the learning code (trpo.TRPO.save / load): the whole record of every environment
+    # the snapshot hooks of the learning code (sampler.Sampler.save / load): the whole record of every environment
     FULL_STATE_WIDTH = STATE_STRIDE
 
     def get_full_state_host(self):

@@ -16,15 +16,17 @@ What rllab's VPG does with these [external: rllab's published source, not on thi
   * vpg_cassie.py's step_size=0.005 and use_gpu=True are swallowed by BatchPolopt's **kwargs: rllab's VPG never reads them.
 
 The sampler, the exploration noise keyed by the global env id, the baseline kernels, advantage centring and the snapshot machinery
-are TRPO's (cassierl_amd/trpo.py), unchanged.  The hot paths of the width-128 policy are HIP kernels (csrc/tu_pg.hip): the policy
+are sampler.OnPolicy's, shared with TRPO and PPO.  The hot paths of the width-128 policy are HIP kernels (csrc/tu_pg.hip): the policy
 step of the sampler, the policy gradient J' w, and the Adam step.
 """
 import torch
 import torch.distributed as dist
 
-from .trpo import (TRPO, FlatAdam, FusedFisher, PgFisher, _two_layer_tanh, _world, all_mean_, broadcast_initial_policy, closed_form_grad, flat_grad, flat_params,
-                   gaussian_policy_nets, hidden_sizes_of, make_cassie_algo, set_flat_params)
-from .trpo import _MEAN_ORDER, adam_step_, fused_adam_step_  # noqa: F401  (defined in trpo.py; tests and tools reach them through this module too)
+from .adam import FlatAdam, adam_step_, fused_adam_step_   # (the two steps: tests and tools call Lasagne's Adam as vpg.adam_step_ / vpg.fused_adam_step_)
+from .comm import _world, all_mean_
+from .fisher import FusedFisher, PgFisher
+from .policy import _MEAN_ORDER, _two_layer_tanh, closed_form_grad, flat_grad, flat_params, hidden_sizes_of, set_flat_params   # (_MEAN_ORDER: as vpg._MEAN_ORDER in tests)
+from .sampler import OnPolicy, broadcast_initial_policy, gaussian_policy_nets, make_cassie_algo
 
 
 class PolicyGradKernels:
@@ -53,8 +55,8 @@ class PolicyGradKernels:
         return flat_grad(loss, self.policy).detach()
 
 
-class VPG(FlatAdam, TRPO):
-    """rllab's VPG on TRPO's sampler and baseline.  Switches (attributes, default True) that tests set to force the torch path:
+class VPG(FlatAdam, OnPolicy):
+    """rllab's VPG on OnPolicy's sampler and baseline.  Switches (attributes, default True) that tests set to force the torch path:
     fused_policy_step (the sampler's policy step), fused_grad (PolicyGradKernels), fused_adam (CassiePgAdam)."""
     ALGO = "vpg"
 
@@ -66,7 +68,7 @@ class VPG(FlatAdam, TRPO):
         self.log_kl = log_kl
         self.last_grad_kind = None
 
-    # the sampler's policy step (CassiePgPolicyStep for a 128-128 policy, CassieTrpoPolicyStep for 32 x 32) is TRPO._fused_policy_step
+    # the sampler's policy step (CassiePgPolicyStep for a 128-128 policy, CassieTrpoPolicyStep for 32 x 32) is OnPolicy._fused_policy_step
 
     def optimize(self, d):
         pol = self.policy
@@ -95,7 +97,7 @@ class VPG(FlatAdam, TRPO):
             st.update(mean_kl=vals[2], max_kl=vals[3], loss_after=vals[4])
         return st
 
-    # ---- snapshot: TRPO's, plus the algorithm, the policy shape, the learning rate and the Adam state
+    # ---- snapshot: Sampler's, plus the algorithm, the policy shape, the learning rate and the Adam state
     def _snapshot_fields(self):
         return dict(super()._snapshot_fields(), learning_rate=float(self.learning_rate), **self._adam_snapshot())
 

@@ -6,6 +6,7 @@ import torch
 from cassierl_amd import ddpg as G
 from cassierl_amd import offpolicy as O
 from cassierl_amd import sac as S
+from cassierl_amd import sampler as SM
 from cassierl_amd import td3 as D3
 from cassierl_amd import trpo as T
 from test_trpo_cpu import ToyVecEnv
@@ -41,15 +42,22 @@ def _toy(name):
 
 def test_the_three_algorithms_derive_from_the_base_and_not_from_each_other():
     for cls in ALGOS.values():
-        assert issubclass(cls, O.OffPolicy) and issubclass(cls, T.TRPO)
+        assert issubclass(cls, O.OffPolicy) and issubclass(cls, SM.Sampler)
+        assert not issubclass(cls, T.TRPO) and not issubclass(cls, SM.OnPolicy)
+    assert issubclass(T.TRPO, SM.Sampler) and not issubclass(O.OffPolicy, T.TRPO)
+    for method in ("optimize", "collect", "process", "_baseline_kernels", "_advantages"):   # what only an on-policy algorithm can run
+        assert not hasattr(O.OffPolicy, method), method
+    for method in ("save", "_book_step", "_reset_truncated", "_fused_sampler_step", "_gather_returns", "_check_env_family"):   # the sampler state and the snapshot
+        assert method in SM.Sampler.__dict__ and method not in O.OffPolicy.__dict__, method
     assert not issubclass(S.SAC, G.DDPG) and not issubclass(D3.TD3, G.DDPG)
     for cls in (G.DdpgKernels, S.SacKernels, D3.Td3Kernels):
         assert issubclass(cls, O.PoolKernels)
 
 
 def test_shared_helpers_are_defined_once():
-    for name in ("ReplayPool", "new_adam", "soft_update_", "_ptrs", "_adam_on", "_NoBaseline", "default_pool_size", "broadcast_initial_networks"):
+    for name in ("ReplayPool", "new_adam", "soft_update_", "_ptrs", "_adam_on", "default_pool_size", "broadcast_initial_networks"):
         assert getattr(G, name) is getattr(O, name), name
+    assert not hasattr(O, "_NoBaseline") and not hasattr(G, "_NoBaseline")   # (stood in for a baseline while OffPolicy derived from TRPO)
     for mod in (S, D3):
         for name in ("new_adam", "soft_update_", "_ptrs", "broadcast_initial_networks"):
             assert getattr(mod, name) is getattr(O, name), (mod.__name__, name)

@@ -1,4 +1,4 @@
-"""The on-policy family's shape (cassierl_amd/trpo.py, vpg.py, ppo.py, es.py): the shared helpers defined once, one kernel-call base, process /
+"""The on-policy family's shape (cassierl_amd/sampler.py, trpo.py, vpg.py, ppo.py, es.py): the shared helpers defined once, one kernel-call base, process /
 save / load / the Adam step / hidden_sizes in one class each, and what each algorithm writes into a snapshot and reports per iteration -- the
 key lists are the ones the four modules had when each carried its own copy."""
 import pytest
@@ -8,6 +8,7 @@ from cassierl_amd import _lib
 from cassierl_amd import es as E
 from cassierl_amd import offpolicy as O
 from cassierl_amd import ppo as P
+from cassierl_amd import sampler as SM
 from cassierl_amd import trpo as T
 from cassierl_amd import vpg as V
 from test_trpo_cpu import ToyVecEnv
@@ -81,12 +82,22 @@ def test_a_call_goes_through_fn_and_a_failure_names_the_symbol():
 
 @pytest.mark.parametrize("name", ["vpg", "ppo", "es"])
 def test_shared_methods_live_in_one_class_alone(name):
+    """Each shared method has one owner: Sampler (what all seven algorithms share), OnPolicy (TRPO, VPG, PPO: the batch and the baseline) or
+    FlatAdam; TRPO owns its own update and nobody derives from it."""
     cls = ALGOS[name]
-    assert issubclass(cls, T.TRPO) and issubclass(cls, T.FlatAdam)
-    for method in ("process", "save", "load", "hidden_sizes", "_baseline_kernels", "_fused_policy_step", "_fused_sampler_step"):
-        assert method not in cls.__dict__ and method in T.TRPO.__dict__, method
+    base = SM.Sampler if name == "es" else SM.OnPolicy   # ES rolls whole episodes out itself: it is on Sampler's snapshot and gather alone
+    assert issubclass(cls, base) and issubclass(cls, T.FlatAdam) and issubclass(SM.OnPolicy, SM.Sampler) and issubclass(T.TRPO, SM.OnPolicy)
+    assert not issubclass(cls, T.TRPO) and (name != "es" or not issubclass(cls, SM.OnPolicy))
+    for method in ("save", "load", "hidden_sizes", "_fused_sampler_step"):
+        assert method not in cls.__dict__ and method not in SM.OnPolicy.__dict__ and method not in T.TRPO.__dict__ and method in SM.Sampler.__dict__, method
+    for method in ("process", "_baseline_kernels", "_fused_policy_step"):
+        assert method not in cls.__dict__ and method not in SM.Sampler.__dict__ and method not in T.TRPO.__dict__ and method in SM.OnPolicy.__dict__, method
+        assert hasattr(cls, method) == (name != "es"), method
+    assert "optimize" in T.TRPO.__dict__ and "optimize" not in SM.OnPolicy.__dict__ and not hasattr(SM.Sampler, "optimize")
+    assert getattr(cls, "optimize", None) is not T.TRPO.optimize   # (the natural gradient, CG and line search: TRPO's alone)
     for method in ("adam_step", "_adam_snapshot", "_adam_load"):
-        assert method not in cls.__dict__ and method not in T.TRPO.__dict__ and method in T.FlatAdam.__dict__, method
+        assert method not in cls.__dict__ and method in T.FlatAdam.__dict__, method
+        assert all(method not in c.__dict__ for c in (T.TRPO, SM.OnPolicy, SM.Sampler)), method
     assert "process" not in O.OffPolicy.__dict__ and "save" not in O.OffPolicy.__dict__ and "hidden_sizes" not in O.OffPolicy.__dict__
 
 

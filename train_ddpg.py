@@ -8,83 +8,32 @@ With --envs-per-gpu 1 these run rllab's loop.  With N environments one vector st
 updates of --batch-size rows (summed over ranks): at large N set both, e.g. `--batch-size 65536 --updates-per-step 1`; no scaling rule is applied.
 """
 import argparse
-import json
 import os
 import sys
-import time
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+from cassierl_amd import train_cli as cli  # noqa: E402
+
+
+def parser():
+    ap = cli.add_common_flags(argparse.ArgumentParser(), timing="report the seconds of an epoch between two synchronisations",
+                              dump_params="after the last epoch rank 0 writes the flat actor, critic and target parameters to this .npy file, rank r > 0 to <file>.rank<r>.npy")
+    return cli.add_pool_flags(ap, batch_size=32, batch_help="rows per update, over all ranks (ddpg_cassie.py: 32)", scale_reward=0.01, qf_learning_rate=1e-3,
+                              policy_learning_rate=1e-4)
+
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--envs-per-gpu", type=int, default=4096)
-    ap.add_argument("--batch-size", type=int, default=32, help="rows per update, over all ranks (ddpg_cassie.py: 32)")
-    ap.add_argument("--updates-per-step", type=int, default=1, help="updates after every vector step (rllab's n_updates_per_sample)")
-    ap.add_argument("--pool-size", type=int, default=0, help="rows of each rank's replay pool, a multiple of --envs-per-gpu (default: 1 000 000 rounded up to one); "
-                    "a row is 4 (2 D + A + 2) bytes = 240 B for the 26-wide observation and 6 actions, so 1 000 000 rows are 240 MB and hold "
-                    "16 vector steps of 65 536 environments")
-    ap.add_argument("--min-pool-size", type=int, default=10000, help="transitions (over all ranks) before the first update")
-    ap.add_argument("--epoch-length", type=int, default=1000, help="vector steps per epoch (one log line, one read-back)")
-    ap.add_argument("--n-epochs", type=int, default=10)
-    ap.add_argument("--max-path-length", type=int, default=100)
-    ap.add_argument("--scale-reward", type=float, default=0.01)
-    ap.add_argument("--qf-learning-rate", type=float, default=1e-3)
-    ap.add_argument("--policy-learning-rate", type=float, default=1e-4)
-    ap.add_argument("--kind", default="walk", choices=["walk", "stand"])
-    ap.add_argument("--control-mode", default="PD", choices=["PD", "Torque", "OSC"])
-    ap.add_argument("--snapshot", default="")
-    ap.add_argument("--snapshot-pool", type=int, default=1, help="0: the snapshot omits the replay pool (it can be gigabytes); a run loaded from it restarts with an empty pool")
-    ap.add_argument("--load-policy", default="")
-    ap.add_argument("--timing", action="store_true", help="report the seconds of an epoch between two synchronisations")
-    ap.add_argument("--torch-update", action="store_true", help="run the torch statements instead of the HIP kernels (A/B)")
-    ap.add_argument("--terrain-dir", default="", help="folder of terrain PNGs (model/terrains/ of the reference): robots on a terrain library")
-    ap.add_argument("--num-terrains", type=int, default=1, help="K fields drawn (with replacement) from --terrain-dir")
-    ap.add_argument("--terrain-elevation", type=float, default=1.0, help="height of a white pixel in metres (the <hfield> size_z)")
-    ap.add_argument("--terrain-seed", type=int, default=1, help="seed of the file draw and of the per-environment field ids")
-    ap.add_argument("--dump-params", default="", help="after the last epoch rank 0 writes the flat actor, critic and target parameters to this .npy file, rank r > 0 to <file>.rank<r>.npy")
-    args = ap.parse_args()
-    import torch
-    from cassierl_amd import rollout as R
+    args = parser().parse_args()
+    rank, world, dev, terrain = cli.setup(args)
     from cassierl_amd.ddpg import make_cassie_ddpg
     from cassierl_amd.trajectory import default_gait
-    rank, local_rank, world = R.init_distributed()
-    dev = R.local_device(local_rank) if world > 1 else 0   # CASSIE_DEVICE_MAP (test hook): several ranks on one GPU
-    torch.cuda.set_device(dev)
-    from cassierl_amd.terrain import terrain_spec
-    terrain = terrain_spec(args.terrain_dir, args.num_terrains, args.terrain_elevation, args.terrain_seed) if args.terrain_dir else None
     algo = make_cassie_ddpg(args.envs_per_gpu, kind=args.kind, control_mode=args.control_mode, device=dev, trajectory=default_gait(), seed=1, terrain=terrain,
-                            replay_pool_size=args.pool_size or None, batch_size=args.batch_size, updates_per_step=args.updates_per_step,
-                            min_pool_size=args.min_pool_size, epoch_length=args.epoch_length, max_path_length=args.max_path_length,
-                            scale_reward=args.scale_reward, qf_learning_rate=args.qf_learning_rate, policy_learning_rate=args.policy_learning_rate,
-                            snapshot_pool=bool(args.snapshot_pool))
-    algo.timing = args.timing
+                            **cli.pool_kwargs(args))
     if args.torch_update:
         algo.fused_update = algo.fused_policy_step = False
-    if args.load_policy:
-        _, restored = algo.load(args.load_policy)
-        if rank == 0:
-            print(json.dumps(dict(loaded=args.load_policy, itr=algo.itr, sampler_restored=restored, pool_restored=algo.pool_restored, pool_size=algo.pool.size)))
-    for _ in range(args.n_epochs):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        st = algo.train_iteration()
-        torch.cuda.synchronize()
-        st["seconds"] = time.perf_counter() - t0
-        st["env_steps_per_s"] = st["env_steps"] / st["seconds"]
-        if rank == 0:
-            print(json.dumps(st), flush=True)
-        if args.snapshot:
-            algo.save(args.snapshot)  # snapshot_mode="last"
-    if args.dump_params:   # rank r > 0 writes <file>.rank<r>.npy: the ranks must hold the same numbers
-        from cassierl_amd.trpo import flat_params
-        np.save(args.dump_params if rank == 0 else "%s.rank%d.npy" % (args.dump_params, rank), torch.cat([flat_params(m) for m in (algo.policy, algo.qf, algo.target_policy, algo.target_qf)]).double().cpu().numpy())
-    if R.dist.is_initialized():
-        R.dist.barrier()
-        R.dist.destroy_process_group()
+    cli.train(algo, args, args.n_epochs, rank, loaded=cli.pool_loaded, dump=cli.pool_dump("policy", "qf", "target_policy", "target_qf"))
 
 
 if __name__ == "__main__":
