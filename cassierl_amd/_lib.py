@@ -43,6 +43,8 @@ EXPORTS = [
     "CassieDdpgParamCount", "CassieDdpgPartialRows", "CassieDdpgPolicyStep", "CassieDdpgPoolCommit", "CassieDdpgCriticGrad", "CassieDdpgActorGrad", "CassieDdpgApply",
     # SAC (include/cassie_trpo.h)
     "CassieSacParamCount", "CassieSacPolicyStep", "CassieSacCriticGrad", "CassieSacActorGrad", "CassieSacApply",
+    # SAC at the Cassie3d shape, 45 x 10 (include/cassie_trpo.h)
+    "CassieSac3dParamCount", "CassieSac3dPolicyStep", "CassieSac3dCriticGrad", "CassieSac3dActorGrad", "CassieSac3dCriticApply", "CassieSac3dActorApply",
     # TD3 (include/cassie_trpo.h)
     "CassieTd3PolicyStep", "CassieTd3CriticGrad", "CassieTd3CriticApply",
     # PPO (include/cassie_trpo.h)

@@ -189,7 +189,7 @@ class DDPG(OffPolicy):
     """rllab's DDPG on OffPolicy's sampler state, pool, schedule and snapshot.  Kernels: CassieDdpgPolicyStep + CassieDdpgPoolCommit per vector step,
     the four update launches; last_update_kind is "ddpg_kernels" or "torch"."""
 
-    ALGO, STEP_ENTRY = "ddpg", "CassieDdpgPolicyStep"
+    ALGO, STEP_ENTRY = "ddpg", {26: "CassieDdpgPolicyStep"}
     NETS = (("policy", "target_policy"), ("qf", "target_qf"))
     ADAMS = ("adam_mu", "adam_q")
     _REW = 3   # _stats: sum (Q - y)^2, sum Q(s, a), sum Q(s, mu(s)), summed mean reward

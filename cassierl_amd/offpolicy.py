@@ -18,6 +18,7 @@ With N environments ("DDPG"):
   6. the per-step exploration normals (DDPG's OU noise) are drawn as TRPO's exploration noise: every rank draws the [n_envs_global][A] normals
      of the job and keeps its shard's rows;
   7. float32 arithmetic.  The update kernels cover D 26 or 17, A 6 or 7, hidden 32 x 32; the policy-step kernels the environment's 26-wide rows.
+     SAC's also cover Cassie3d's 45 x 10 (sac.py; DDPG and TD3 do not run on env="cassie3d").
 
 A new algorithm on the pool: DESIGN.md, "Off-policy family".
 """
@@ -145,7 +146,7 @@ class OffPolicy(Sampler):
     attributes and hooks below, _explore, update and its own constructor arguments ("Off-policy family")."""
 
     ALGO = None         # the snapshot's "algo" entry
-    STEP_ENTRY = None   # exported name of the policy-step kernel
+    STEP_ENTRY = {}     # width of the environment's rows -> exported name of the policy-step kernel for it (26; SAC: 45 as well)
     NETS = ()           # (live, target or None) attribute names, the actor ("policy") first: targets are made, saved and broadcast from this
     ADAMS = ()          # attribute names of the Adam states
     COUNTS = ()         # keys of _report() that follow "updates" in the epoch's dict; the others follow "avg_return"
@@ -237,17 +238,18 @@ class OffPolicy(Sampler):
         return self._kernels or None
 
     def _fused_step(self, dev):
-        """(policy step, pool commit) as one launch each, or None: CUDA float32 networks of a supported shape on the environment's 26-wide rows,
-        rllab's normalize() action map with float64 bounds."""
-        if not getattr(self, "fused_policy_step", True) or dev.type != "cuda" or not self._covered() or self.obs_dim != 26 or self.policy.obs_dim != 26 \
+        """(policy step, pool commit) as one launch each, or None: CUDA float32 networks of a supported shape on the environment's own rows (26 wide;
+        45 wide where the algorithm has a step entry for it), rllab's normalize() action map with float64 bounds."""
+        entry = self.STEP_ENTRY.get(self.obs_dim)
+        if not getattr(self, "fused_policy_step", True) or dev.type != "cuda" or not self._covered() or entry is None or self.policy.obs_dim != self.obs_dim \
                 or not isinstance(self.act_map, NormalizedActions):
             return None
         low, high, n, D, A = self.act_map.low, self.act_map.high, self.n_envs, self.obs_dim, self.act_dim
         if not all(t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == A for t in (low, high)):
             return None
-        if not available(self.STEP_ENTRY, "CassieDdpgPoolCommit"):
+        if not available(entry, "CassieDdpgPoolCommit"):
             return None
-        k = Kernels(dev, entry={"Step": self.STEP_ENTRY, "Commit": "CassieDdpgPoolCommit"})
+        k = Kernels(dev, entry={"Step": entry, "Commit": "CassieDdpgPoolCommit"})
         step_fn, commit_fn = k.fn["Step"], k.fn["Commit"]
         if not hasattr(self, "_env_actions") or self._env_actions.shape != (n, A):
             self._env_actions = torch.empty((n, A), dtype=torch.float64, device=dev)
@@ -256,13 +258,13 @@ class OffPolicy(Sampler):
 
         def step(obs, noise, top):
             if obs.dtype != torch.float64 or not obs.is_contiguous():
-                raise TypeError("%s: observations must be a contiguous float64 tensor (got %s)" % (self.STEP_ENTRY, obs.dtype))
+                raise TypeError("%s: observations must be a contiguous float64 tensor (got %s)" % (entry, obs.dtype))
             assert noise.is_contiguous() and noise.dtype == torch.float32 and noise.shape == (n, A)
             assert 0 <= top and top + n <= pool.capacity
             rc = self._policy_step_call(step_fn, (_P(obs), n, D, A), _P(noise),
                                         (_P(low), _P(high), _P(pool.obs[top]), _P(pool.act[top]), _P(self._env_actions), stream()))
             if rc != 0:
-                raise RuntimeError("%s failed (%d)" % (self.STEP_ENTRY, rc))
+                raise RuntimeError("%s failed (%d)" % (entry, rc))
         return step, self._pool_commit(commit_fn, stream)
 
     def _pool_commit(self, commit_fn, stream):
@@ -366,6 +368,7 @@ class OffPolicy(Sampler):
         algo = ck.get("algo", "trpo")
         if algo != self.ALGO:
             raise ValueError("%s.load: the snapshot was written by %s, this run is %s" % (type(self).__name__, algo, self.ALGO))
+        self._check_env_family(ck)   # before the first network comes back: the other family's networks have other shapes
         for name in self._saved_nets():
             getattr(self, name).load_state_dict(ck[name])
         for name in self.ADAMS:

@@ -33,6 +33,11 @@ Hot paths are HIP kernels (csrc/tu_sac.hip, include/cassie_trpo.h): CassieSacPol
 CassieSacCriticGrad (both critics, one launch), CassieDdpgApply for each critic, CassieSacActorGrad, CassieSacApply (actor and log_alpha): five
 launches.  Each has its torch statement in this module (SquashedGaussianMLPPolicy.sample, sac_update_torch_); CPU tensors, other shapes or a
 library without the entry points run those.
+
+On Cassie3d (make_cassie_sac(n, env="cassie3d", control_mode="PD" | "Torque", kp=.., kd=..): 45 observations, 10 actions, the standing reset) the
+same 32 x 32 networks run on the kernels of csrc/tu_sac3d.hip -- CassieSac3dPolicyStep, CassieSac3dCriticGrad, CassieSac3dCriticApply for each critic,
+CassieSac3dActorGrad, CassieSac3dActorApply, still five launches per update -- and everything above holds unchanged: target_entropy defaults to -10,
+and a pool row is 4 (2 D + A + 2) = 408 bytes, so the default pool of 1 000 000 rows is 408 MB per rank.
 """
 import ctypes as ct
 import math
@@ -44,7 +49,7 @@ from torch.nn import functional as F
 
 from .adam import adam_step_
 from .comm import all_mean_
-from .ddpg import CRITIC, ContinuousMLPQFunction, _init_hidden, _init_output
+from .ddpg import ACTOR, CRITIC, ContinuousMLPQFunction, _init_hidden, _init_output
 from .offpolicy import OffPolicy, PoolKernels, _F, _P, _adam_on, _ptrs, broadcast_initial_networks, make_cassie_offpolicy, new_adam, soft_update_
 
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
@@ -115,29 +120,39 @@ def sac_update_torch_(actor, qf1, qf2, target_qf1, target_qf2, log_alpha, adam_p
     return losses[0], losses[1], policy_loss.detach(), avg_logp, alpha.reshape(())
 
 
+SHAPE3D = (45, 10)   # Cassie3d: the kernels of csrc/tu_sac3d.hip
+
+
 def kernels_cover(actor, qf1, qf2):
-    """The kernels' shapes: float32 CUDA networks, hidden 32 x 32, D 26 or 17, A 6 or 7."""
+    """The kernels' shapes: float32 CUDA networks, hidden 32 x 32, D 26 or 17 with A 6 or 7, or Cassie3d's (45, 10)."""
     if not isinstance(actor, SquashedGaussianMLPPolicy) or not all(isinstance(q, ContinuousMLPQFunction) for q in (qf1, qf2)):
         return False
     if not all(p.is_cuda and p.dtype == torch.float32 for p in (next(m.parameters()) for m in (actor, qf1, qf2))):
         return False
-    return actor.hidden_sizes == (32, 32) and actor.obs_dim in (26, 17) and actor.act_dim in (6, 7) \
+    return actor.hidden_sizes == (32, 32) and ((actor.obs_dim in (26, 17) and actor.act_dim in (6, 7)) or (actor.obs_dim, actor.act_dim) == SHAPE3D) \
         and all(q.hidden_sizes == (32, 32) and (q.obs_dim, q.act_dim) == (actor.obs_dim, actor.act_dim) for q in (qf1, qf2))
 
 
 class SacKernels(PoolKernels):
-    """The five launches of one update (csrc/tu_sac.hip, tu_ddpg.hip's apply) on the networks' own storage.  ValueError / OSError / AttributeError
-    where they do not apply."""
+    """The five launches of one update (csrc/tu_sac.hip, tu_ddpg.hip's apply; at 45 x 10 csrc/tu_sac3d.hip, ENTRY3D) on the networks' own storage.
+    ValueError / OSError / AttributeError where they do not apply."""
 
     ENTRY = dict(PartialRows="CassieDdpgPartialRows", ParamCount="CassieDdpgParamCount", SacParamCount="CassieSacParamCount", SacCriticGrad="CassieSacCriticGrad",
                  SacActorGrad="CassieSacActorGrad", SacApply="CassieSacApply", Apply="CassieDdpgApply")
+    ENTRY3D = dict(PartialRows="CassieDdpgPartialRows", ParamCount="CassieSac3dParamCount", SacCriticGrad="CassieSac3dCriticGrad",
+                   SacActorGrad="CassieSac3dActorGrad", SacApply="CassieSac3dActorApply", Apply="CassieSac3dCriticApply")
 
     def __init__(self, actor, qf1, qf2, target_qf1, target_qf2, log_alpha):
         if not kernels_cover(actor, qf1, qf2):
-            raise ValueError("SacKernels: float32 CUDA networks with 32 x 32 hidden units, obs_dim 26 or 17, act_dim 6 or 7")
-        super().__init__((actor, qf1, qf2, target_qf1, target_qf2))
+            raise ValueError("SacKernels: float32 CUDA networks with 32 x 32 hidden units, obs_dim 26 or 17 and act_dim 6 or 7, or 45 x 10")
         self.D, self.A = actor.obs_dim, actor.act_dim
-        self.np_pi, self.np_q = self.fn["SacParamCount"](self.D, self.A), self.fn["ParamCount"](self.D, self.A, CRITIC)
+        self.is3d = (self.D, self.A) == SHAPE3D
+        if self.is3d:
+            self.ENTRY = self.ENTRY3D   # the entry table of this shape
+        super().__init__((actor, qf1, qf2, target_qf1, target_qf2))
+        self.np_pi = self.fn["ParamCount"](self.D, self.A, ACTOR) if self.is3d else self.fn["SacParamCount"](self.D, self.A)
+        self.np_q = self.fn["ParamCount"](self.D, self.A, CRITIC)
+        self._which = () if self.is3d else (CRITIC,)   # CassieDdpgApply serves both of DDPG's networks; CassieSac3dCriticApply is the critic's
         if self.np_pi == 0 or self.np_q == 0:
             raise ValueError("SacKernels: unsupported shape %d -> %d" % (self.D, self.A))
         if not (log_alpha.is_cuda and log_alpha.dtype == torch.float32 and log_alpha.numel() == 1):
@@ -162,9 +177,9 @@ class SacKernels(PoolKernels):
         return out
 
     def critic_apply(self, k, partial, scale, adam, lr, beta1, beta2, eps, tau, stats=None):
-        """CassieDdpgApply on critic k: rows added in order, Adam, soft update of its target.  stats [2] float64: += (sum (Q - y)^2, sum Q)."""
+        """CassieDdpgApply (45 x 10: CassieSac3dCriticApply) on critic k: rows added in order, Adam, soft update of its target.  stats [2] float64: += (sum (Q - y)^2, sum Q)."""
         adam["t"] += 1
-        self._call("Apply", partial.shape[0], self.D, self.A, CRITIC, _P(partial), ct.c_float(scale), _ptrs(self.qf[k]), _ptrs(self.target_qf[k]), _P(adam["m"]),
+        self._call("Apply", partial.shape[0], self.D, self.A, *self._which, _P(partial), ct.c_float(scale), _ptrs(self.qf[k]), _ptrs(self.target_qf[k]), _P(adam["m"]),
                    _P(adam["v"]), int(adam["t"]), *_F(lr, beta1, beta2, eps, tau), None if stats is None else _P(stats), self._stream())
 
     def actor_apply(self, partial, scale, adam, lr, beta1, beta2, eps, adam_alpha, alpha_lr, target_entropy, stats=None):
@@ -194,7 +209,8 @@ class SAC(OffPolicy):
     """Soft Actor-Critic on OffPolicy's sampler state, pool, schedule and snapshot.  Kernels: CassieSacPolicyStep + CassieDdpgPoolCommit per vector step,
     the five update launches; last_update_kind is "sac_kernels" or "torch"."""
 
-    ALGO, STEP_ENTRY = "sac", "CassieSacPolicyStep"
+    ALGO, STEP_ENTRY = "sac", {26: "CassieSacPolicyStep", 45: "CassieSac3dPolicyStep"}
+    CASSIE3D = True
     NETS = (("policy", None), ("qf1", "target_qf1"), ("qf2", "target_qf2"))   # there is no target actor
     ADAMS = ("adam_pi", "adam_q1", "adam_q2", "adam_alpha")
     _REW = 7   # _stats: sum e1^2, sum Q1, sum e2^2, sum Q2, sum log pi, sum min Q, summed actor loss, summed mean reward
@@ -281,6 +297,8 @@ class SAC(OffPolicy):
 
 
 def make_cassie_sac(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, terrain=None, sync_policy=True, replay_pool_size=None, **kw):
-    """SAC on the batched MI355X environment: offpolicy.make_cassie_offpolicy with SAC's networks."""
+    """SAC on the batched MI355X environment: offpolicy.make_cassie_offpolicy with SAC's networks.  env="cassie3d" (with control_mode and, through **kw,
+    kp / kd) runs it on Cassie3dVecEnv: sampler.make_cassie_algo.  replay_pool_size defaults to 1 000 000 rows per rank: 240 MB on Cassie2d, 408 MB
+    on Cassie3d (a row is 4 (2 D + A + 2) bytes)."""
     make_nets = lambda D, A: (SquashedGaussianMLPPolicy(D, A), ContinuousMLPQFunction(D, A), ContinuousMLPQFunction(D, A))
     return make_cassie_offpolicy(SAC, make_nets, n_envs, kind, control_mode, device, trajectory, seed, terrain, sync_policy, replay_pool_size, **kw)

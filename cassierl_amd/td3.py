@@ -133,7 +133,7 @@ class TD3(OffPolicy):
     """TD3 on OffPolicy's sampler state, pool, schedule and snapshot.  Kernels: CassieTd3PolicyStep + CassieDdpgPoolCommit per vector step, the
     update launches; last_update_kind is "td3_kernels" or "torch"."""
 
-    ALGO, STEP_ENTRY = "td3", "CassieTd3PolicyStep"
+    ALGO, STEP_ENTRY = "td3", {26: "CassieTd3PolicyStep"}
     NETS = (("policy", "target_policy"), ("qf1", "target_qf1"), ("qf2", "target_qf2"))
     ADAMS = ("adam_mu", "adam_q1", "adam_q2")
     COUNTS = ("actor_updates",)

@@ -308,6 +308,35 @@ int CassiePg3dClipGrad(const float* obs_dev, int n, int obs_dim, int act_dim, co
                        const float* old_mean_dev, const float* log_std_old, const float* log_std_new, float clip, float scale, float* partial_dev,
                        double* stats_dev, void* stream);
 
+/* ---- SAC at 45 x 10: Soft Actor-Critic on Cassie3d (cassierl_amd/sac.py with env="cassie3d", csrc/tu_sac3d.hip, csrc/mlp32_tiles3d.h).  The networks
+ * are still the 32 x 32 ReLU networks above: the actor's W1 [32][45], W3 [20][32] (mean rows [0, 10), log_std rows [10, 20)), a critic's W1 [32][45],
+ * W2 [32][42].  The contracts of CassieSacPolicyStep, CassieSacCriticGrad, CassieSacActorGrad and CassieSacApply (here CassieSac3dActorApply) for the
+ * one shape obs_dim = 45, act_dim = 10; any other shape, a null pointer, batch / n / rows <= 0 or a misaligned pointer is CASSIE_EINVAL before
+ * anything is launched.  CassieDdpgApply and CassieSacApply keep refusing this shape: a critic's Adam step and soft update is
+ * CassieSac3dCriticApply (CassieDdpgApply's contract for the critic, 2 statistics columns).  The rows of partial sums of a batch are
+ * CassieDdpgPartialRows(batch), the pool commit is CassieDdpgPoolCommit (both shape-free).  One update is five launches: CassieSac3dCriticGrad,
+ * CassieSac3dCriticApply for each critic, CassieSac3dActorGrad, CassieSac3dActorApply.  Every sum runs in a fixed order: a call repeats bit for bit. */
+
+/* parameters of the actor (which = CASSIE_DDPG_ACTOR: 3188) or of a critic (CASSIE_DDPG_CRITIC: 2881); 0 for any other shape.  Host only. */
+int CassieSac3dParamCount(int obs_dim, int act_dim, int which);
+int CassieSac3dPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* const* actor, const float* noise_dev, const double* low_dev,
+                          const double* high_dev, float* pool_obs_row_dev, float* pool_act_row_dev, double* env_actions_dev, void* stream);
+/* partial [2][CassieDdpgPartialRows(batch)][2881 + 2] */
+int CassieSac3dCriticGrad(const float* pool_obs, const float* pool_act, const float* pool_rew, const float* pool_term, const float* pool_next_obs,
+                          long long pool_capacity, const long long* idx_dev, int batch, int obs_dim, int act_dim, const float* const* actor,
+                          const float* const* target_qf1, const float* const* target_qf2, const float* const* qf1, const float* const* qf2,
+                          const float* eps_next_dev, const float* log_alpha_dev, float discount, float* partial_dev, void* stream);
+/* partial [CassieDdpgPartialRows(batch)][3188 + 2] */
+int CassieSac3dActorGrad(const float* pool_obs, long long pool_capacity, const long long* idx_dev, int batch, int obs_dim, int act_dim, const float* const* actor,
+                         const float* const* qf1, const float* const* qf2, const float* eps_dev, const float* log_alpha_dev, float* partial_dev, void* stream);
+/* One launch, one workgroup, on one critic's block [rows][2881 + 2]: g = scale * (the rows added in order);  Adam on `live` (t = the step count after
+ * its increment);  target <- (1 - tau) target + tau live;  stats_dev[0 .. 1] += (sum e^2, sum Q) (float64; NULL: not recorded). */
+int CassieSac3dCriticApply(int rows, int obs_dim, int act_dim, const float* partial_dev, float scale, float* const* live, float* const* target, float* m_dev,
+                           float* v_dev, int t, float lr, float beta1, float beta2, float eps, float tau, double* stats_dev, void* stream);
+int CassieSac3dActorApply(int rows, int obs_dim, int act_dim, const float* partial_dev, float scale, float* const* actor, float* m_dev, float* v_dev, int t, float lr,
+                          float beta1, float beta2, float eps, float* log_alpha_dev, float* alpha_m_dev, float* alpha_v_dev, int alpha_t, float alpha_lr,
+                          float target_entropy, double* stats_dev, void* stream);
+
 /* ---- ES (cassierl_amd/es.py, csrc/tu_es.hip): antithetic perturbations of the 32 x 32 tanh mean network drawn from a shared noise table.
  * theta [P] is the mean network's parameter row [W1 | b1 | W2 | b2 | W3 | b3] (row-major as torch.nn.Linear), P = CassieEsParamCount; table
  * [table_len] float32 holds standard normal numbers; direction d is eps_d = table[offsets[d] : offsets[d] + P].  Environment i evaluates

@@ -69,8 +69,12 @@ def main():
         args.deterministic = True
     elif ck.get("algo") == "sac":   # a train_sac.py snapshot: the squashed Gaussian; only the actor is loaded, so the smallest pool will do
         from cassierl_amd.sac import make_cassie_sac
-        algo = make_cassie_sac(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
-                               terrain=terrain, replay_pool_size=args.envs)
+        if ck.get("env_family", "cassie2d") == "cassie3d":   # written by train_sac.py --env cassie3d: the control mode and gains are the snapshot's
+            cfg = ck["env_config"]
+            env_kw = dict(env="cassie3d", control_mode=cfg["control_mode"], kp=cfg["kp"], kd=cfg["kd"])
+        else:
+            env_kw = dict(kind=args.kind, control_mode=args.control_mode, trajectory=default_gait(), terrain=terrain)
+        algo = make_cassie_sac(args.envs, device=0, seed=args.seed, replay_pool_size=args.envs, **env_kw)
     else:   # a train_trpo.py snapshot: 32 x 32 unless it records other hidden sizes
         algo = make_cassie_trpo(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed,
                                 terrain=terrain, hidden_sizes=tuple(ck.get("hidden_sizes", (32, 32))))
