@@ -54,6 +54,9 @@ EXPORTS = [
     # ES (include/cassie_trpo.h)
     "CassieEsParamCount", "CassieEsPairsPerWorkgroup", "CassieEsPolicyStep", "CassieEsBook", "CassieEsGradRows", "CassieEsGrad",
     "CassieEsWideParamCount", "CassieEsWidePairsPerWorkgroup", "CassieEsWidePolicyStep",
+    # ES at the Cassie3d shape, 45 x 10 (include/cassie_trpo.h)
+    "CassieEs3dParamCount", "CassieEs3dPairsPerWorkgroup", "CassieEs3dPolicyStep",
+    "CassieEs3dWideParamCount", "CassieEs3dWidePairsPerWorkgroup", "CassieEs3dWidePolicyStep",
 ]
 
 

@@ -2,18 +2,19 @@
 for a whole episode, nothing is stored per step, and the update is one weighted sum of noise vectors.
 
 There is no reference counterpart (rllab ships the family as CEM / CMA-ES and no script of the reference uses it): the torch statements in this
-module are the specification, the kernels of csrc/tu_es.hip (and, for the 128 x 128 policy's step, csrc/tu_es_wide.hip) evaluate them.
+module are the specification, the kernels of csrc/tu_es.hip (and, for the 128 x 128 policy's step, csrc/tu_es_wide.hip; for both widths at Cassie3d's
+shape, 45 observations and 10 actions, csrc/tu_es3d.hip) evaluate them.
 
   parameters  theta = flat_params(policy.mean_net), the row [W1 | b1 | W2 | b2 | W3 | b3] (policy._MEAN_ORDER, the actor row of csrc/mlp32_tiles.h),
               P entries: 2118 for the shape (26, 6), 2151 for (26, 7), 1863 for (17, 7) at 32 x 32 hidden units; 20 742, 20 871 and 19 719 at
-              128 x 128 (19 590 for (17, 6)).  log_std is never touched, so a TRPO run can load an ES snapshot and continue from it.
+              128 x 128 (19 590 for (17, 6)); 2858 and 23 690 for Cassie3d's (45, 10).  log_std is never touched, so a TRPO run can load an ES snapshot and continue from it.
   noise       table = randn(table_size) float32 on the device from a generator seeded by table_seed (default 1 << 24 entries, 64 MB): regenerated
               from the seed on load, never written to a snapshot.
   population  n_envs (even) per rank; local environment i evaluates direction d = i >> 1 with sign s = +1 (i even) or -1 (i odd), direction d is
               eps_d = table[off_d : off_d + P].  The offsets of ALL ranks are drawn once per iteration, randint(0, table_size - P + 1, (M_global,)),
               from a generator seeded identically on every rank; a rank keeps its shard (TRPO's rule for the exploration noise: a run does not
               depend on how the environments are sharded).
-  action      (es_actions_torch; CassieEsPolicyStep, CassieEsWidePolicyStep at width 128)  w_i = theta + (s_i sigma) eps_(i >> 1);  mean_i = W3 tanh(W2 tanh(W1 obs_i + b1) + b2) + b3
+  action      (es_actions_torch; CassieEsPolicyStep, CassieEsWidePolicyStep at width 128, CassieEs3dPolicyStep / CassieEs3dWidePolicyStep at 45 x 10)  w_i = theta + (s_i sigma) eps_(i >> 1);  mean_i = W3 tanh(W2 tanh(W1 obs_i + b1) + b2) + b3
               with the layers cut out of w_i;  act_i = alive_i ? mean_i : 0;  env_action_i = NormalizedActions(act_i): a dead environment gets
               the middle of the box.
   rollout     reset every environment, then up to max_path_length steps with (es_book_torch; CassieEsBook)
@@ -28,7 +29,8 @@ module are the specification, the kernels of csrc/tu_es.hip (and, for the 128 x 
 Defaults are OpenAI's: sigma 0.02, learning_rate 0.01, l2_coeff 0.005; max_path_length 1000.  The snapshot machinery and the gather are sampler.Sampler's,
 shared with every other algorithm.  The 32 x 32 and the 128 x 128 policy in float32 on the GPU have kernels (the policy step is one kernel per width;
 the bookkeeping, the gradient and Adam do not see the width); other hidden sizes, CPU tensors, float64 or a library without the symbols -- one
-without the CassieEsWide* symbols at width 128 only -- take the torch statements.
+without the CassieEsWide* symbols at width 128 only, or the CassieEs3d* ones at 45 x 10 only -- take the torch statements.  On Cassie3d
+(make_cassie_es(env="cassie3d")) nothing else changes: the perturbation is in the parameters, once per episode, and no noise is put on the actions.
 """
 import ctypes as ct
 import time
@@ -115,31 +117,39 @@ def pair_weights(u):
 
 # --------------------------------------------------------------------------------------------- the kernel-call layer
 class EsKernels(Kernels):
-    """The library calls of ES on one noise table (csrc/tu_es.hip, csrc/tu_es_wide.hip).  ENTRY names the exported functions; every call goes through
+    """The library calls of ES on one noise table (csrc/tu_es.hip, csrc/tu_es_wide.hip, csrc/tu_es3d.hip).  ENTRY names the exported functions; every call goes through
     the dict `fn` (key -> function, looked up at call time, so a test can wrap its entries).  `hidden` = (128, 128) puts the Wide* functions under
-    the keys ParamCount, PairsPerWorkgroup and PolicyStep (entry_for); an object looks up the symbols of its own width only.  The kernels do not
+    the keys ParamCount, PairsPerWorkgroup and PolicyStep, the shape (45, 10) the 3d* / 3dWide* ones (entry_for); an object looks up the symbols of
+    its own width and shape only.  The kernels do not
     check offsets: set_directions does, on the host, with one read-back, and raises before anything is launched.  ValueError for an unsupported
     shape or width, or a table that is not a contiguous float32 vector."""
 
     ENTRY = {"ParamCount": "CassieEsParamCount", "PairsPerWorkgroup": "CassieEsPairsPerWorkgroup", "PolicyStep": "CassieEsPolicyStep", "Book": "CassieEsBook",
              "GradRows": "CassieEsGradRows", "Grad": "CassieEsGrad",
-             "WideParamCount": "CassieEsWideParamCount", "WidePairsPerWorkgroup": "CassieEsWidePairsPerWorkgroup", "WidePolicyStep": "CassieEsWidePolicyStep"}
+             "WideParamCount": "CassieEsWideParamCount", "WidePairsPerWorkgroup": "CassieEsWidePairsPerWorkgroup", "WidePolicyStep": "CassieEsWidePolicyStep",
+             "3dParamCount": "CassieEs3dParamCount", "3dPairsPerWorkgroup": "CassieEs3dPairsPerWorkgroup", "3dPolicyStep": "CassieEs3dPolicyStep",
+             "3dWideParamCount": "CassieEs3dWideParamCount", "3dWidePairsPerWorkgroup": "CassieEs3dWidePairsPerWorkgroup",
+             "3dWidePolicyStep": "CassieEs3dWidePolicyStep"}
+    SHAPE3D = (45, 10)   # Cassie3d's observations and actions: the shape of the 3d* entries
 
     @classmethod
-    def entry_for(cls, hidden):
-        """key -> exported name for the policy width `hidden`: (32, 32) or (128, 128)."""
+    def entry_for(cls, hidden, shape=None):
+        """key -> exported name for the policy width `hidden`, (32, 32) or (128, 128), and the shape (obs_dim, act_dim): (45, 10) takes the
+        kernels of csrc/tu_es3d.hip, any other shape (or none) those of tu_es.hip / tu_es_wide.hip."""
         hidden = tuple(int(x) for x in hidden)
-        entry = {k: v for k, v in cls.ENTRY.items() if not k.startswith("Wide")}
-        if hidden == (128, 128):
-            entry.update({k[4:]: v for k, v in cls.ENTRY.items() if k.startswith("Wide")})
-        elif hidden != (32, 32):
+        if hidden not in ((32, 32), (128, 128)):
             raise ValueError("EsKernels: hidden sizes %r have no kernels (32 x 32 and 128 x 128 do)" % (hidden,))
+        entry = {k: v for k, v in cls.ENTRY.items() if not k.startswith(("Wide", "3d"))}
+        prefix = ("3d" if shape is not None and tuple(int(x) for x in shape) == cls.SHAPE3D else "") + ("Wide" if hidden == (128, 128) else "")
+        if prefix:
+            entry.update({k: cls.ENTRY[prefix + k] for k in ("ParamCount", "PairsPerWorkgroup", "PolicyStep")})
         return entry
 
     def __init__(self, table, n_envs, obs_dim, act_dim, low=None, high=None, hidden=(32, 32)):
-        super().__init__(table.device, entry=self.entry_for(hidden))
+        super().__init__(table.device, entry=self.entry_for(hidden, (obs_dim, act_dim)))
         self.hidden = tuple(int(x) for x in hidden)
         self.D, self.A, self.n = int(obs_dim), int(act_dim), int(n_envs)
+        self.step_kind = ("es3d" if (self.D, self.A) == self.SHAPE3D else "es") + ("_wide_step" if self.hidden == (128, 128) else "_step")
         self.P = self.fn["ParamCount"](self.D, self.A)
         if self.P == 0:
             raise ValueError("EsKernels: unsupported policy shape %d -> %d" % (self.D, self.A))
@@ -173,7 +183,7 @@ class EsKernels(Kernels):
 
     def policy_step(self, obs, theta, sigma, alive=None, out=None):
         """env_actions [n, act_dim] float64 of the population at obs [n, obs_dim] float64 (CassieEsPolicyStep or CassieEsWidePolicyStep); alive
-        uint8 [n] or None."""
+        uint8 [n] or None.  (At 45 x 10: CassieEs3dPolicyStep or CassieEs3dWidePolicyStep.)"""
         if self.offsets is None or self._dir_np != self.P:
             raise ValueError("EsKernels.policy_step: set_directions first")
         if obs.dtype != torch.float64 or not obs.is_contiguous() or obs.shape != (self.n, self.D) or obs.device != self.dev:
@@ -229,8 +239,9 @@ def make_table(size, seed, device):
 class ES(FlatAdam, Sampler):
     """ES on Sampler's snapshot machinery and gather; the baseline the constructor takes (the on-policy family's signature) is unused.  Switches (attributes, default True) that tests set to force the torch
     statements: fused_policy_step (CassieEsPolicyStep), fused_book (CassieEsBook), fused_grad (CassieEsGrad), fused_adam (CassiePgAdam).
-    last_policy_step_kind ("es_step" / "es_wide_step" at width 128 / "torch"), last_book_fused, last_grad_kind ("es_grad" / "torch") and last_adam_fused say what ran."""
+    last_policy_step_kind ("es_step" / "es_wide_step" at width 128, "es3d_step" / "es3d_wide_step" on Cassie3d, or "torch"), last_book_fused, last_grad_kind ("es_grad" / "torch") and last_adam_fused say what ran."""
     ALGO = "es"
+    CASSIE3D = True   # make_cassie_es(env="cassie3d"): csrc/tu_es3d.hip
 
     def __init__(self, env_step, env_reset, policy, baseline, n_envs, obs_dim, act_map, sigma=0.02, learning_rate=0.01, l2_coeff=0.005, max_path_length=1000,
                  table_size=1 << 24, table_seed=None, fitness_shaping="centered_rank", beta1=0.9, beta2=0.999, epsilon=1e-8, seed=1, env_reset_masked=None,
@@ -272,7 +283,7 @@ class ES(FlatAdam, Sampler):
         if lin[0].in_features != self.obs_dim or not all(t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == A for t in (low, high)):
             return None
         # no library, one without the symbols or an unsupported shape: the torch statements.  Anything else EsKernels objects to is a mistake and raises.
-        entry = EsKernels.entry_for(self.hidden_sizes)   # (the symbols of this width only: a library without the wide ones still serves 32 x 32)
+        entry = EsKernels.entry_for(self.hidden_sizes, (self.obs_dim, A))   # (the symbols of this width and shape only: a library without the wide ones still serves 32 x 32)
         if not available(*entry.values()) or Kernels(p.device, entry={"ParamCount": entry["ParamCount"]}).fn["ParamCount"](self.obs_dim, A) == 0:
             return None
         self._ek = None   # (a refusal below is raised again by the next call, not remembered as 'torch')
@@ -305,7 +316,7 @@ class ES(FlatAdam, Sampler):
         alive = torch.ones(n, dtype=torch.uint8, device=dev)
         step_fused = ek is not None and getattr(self, "fused_policy_step", True)
         book_fused = ek is not None and getattr(self, "fused_book", True)
-        self.last_policy_step_kind, self.last_book_fused = ("es_wide_step" if ek.hidden == (128, 128) else "es_step") if step_fused else "torch", False
+        self.last_policy_step_kind, self.last_book_fused = ek.step_kind if step_fused else "torch", False
         for t in range(self.max_path_length):
             if step_fused:
                 actions = ek.policy_step(obs, theta, self.sigma, alive)
@@ -388,7 +399,8 @@ class ES(FlatAdam, Sampler):
 
 
 def make_cassie_es(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, hidden_sizes=(32, 32), terrain=None, sync_policy=True, **kw):
-    """ES on the batched MI355X environment; the counterpart of ppo.make_cassie_ppo (same env and sync_policy rules).  With a terrain library both
+    """ES on the batched MI355X environment; the counterpart of ppo.make_cassie_ppo (same env and sync_policy rules; env="cassie3d", control_mode
+    "PD" / "Torque", kp, kd: Cassie3dVecEnv, sampler.make_cassie_algo).  With a terrain library both
     environments of a pair stand on the same field (ids drawn over env_ids // 2): otherwise the antithetic difference would measure the ground,
     not the perturbation."""
     return make_cassie_algo(ES, gaussian_policy_nets(hidden_sizes, 1.0), broadcast_initial_policy, n_envs, kind, control_mode, device, trajectory, seed, terrain,

@@ -22,7 +22,7 @@ from .policy import GaussianMLPPolicy, NormalizedActions, _two_layer_tanh, flat_
 
 class Sampler:
     ALGO = None        # the snapshot's "algo" entry ("trpo": a plain TRPO snapshot has none)
-    CASSIE3D = False   # whether make_cassie_algo builds this algorithm on Cassie3d (env="cassie3d"): PPO and SAC
+    CASSIE3D = False   # whether make_cassie_algo builds this algorithm on Cassie3d (env="cassie3d"): PPO, SAC and ES
 
     def __init__(self, env_step, env_reset, policy, n_envs, obs_dim, act_map, batch_size, max_path_length=1000, discount=0.99, seed=1, env_reset_masked=None,
                  env_id0=None):
@@ -405,7 +405,7 @@ def make_cassie_algo(cls, make_nets, broadcast, n_envs, kind="walk", control_mod
                      terrain_ids=None, env="cassie2d", kp=10.0, kd=5.0, **kw):
     """cls on the batched MI355X environment: what every make_cassie_* is.  env: the environment family -- "cassie2d" (CassieVecEnv: kind, trajectory,
     terrain) or "cassie3d" (Cassie3dVecEnv(n_envs, control_mode, kp, kd): standing reset, 45 observations, 10 actions; no terrain, gait or kind, and
-    only for an algorithm with CASSIE3D set -- PPO and SAC; the others refuse rather than run untested on their torch paths).  make_nets(obs_dim, act_dim, dev) -> the constructor's arguments between
+    only for an algorithm with CASSIE3D set -- PPO, SAC and ES; the others refuse rather than run untested on their torch paths).  make_nets(obs_dim, act_dim, dev) -> the constructor's arguments between
     env_reset and n_envs (the policy first), built right after torch.manual_seed(seed): every rank builds the same initial networks, and with
     sync_policy `broadcast(algo)` makes rank 0's authoritative anyway.  sync_policy=False: NOTHING collective happens in here (the env, its
     workspaces, the networks are local allocations that can fail on one rank alone); the caller agrees on success across ranks first and then
@@ -416,7 +416,7 @@ def make_cassie_algo(cls, make_nets, broadcast, n_envs, kind="walk", control_mod
     family, env_config = env, None
     if family == "cassie3d":   # (checked before any device is touched)
         if not cls.CASSIE3D:
-            raise ValueError("%s does not run on env='cassie3d': PPO (ppo.make_cassie_ppo) and SAC (sac.make_cassie_sac) are the algorithms built for the 45 x 10 shape" % cls.__name__)
+            raise ValueError("%s does not run on env='cassie3d': PPO (ppo.make_cassie_ppo), SAC (sac.make_cassie_sac) and ES (es.make_cassie_es) are the algorithms built for the 45 x 10 shape" % cls.__name__)
         if terrain is not None or trajectory is not None or kind != "walk":
             raise ValueError("env='cassie3d' has no terrain, reference gait or kind (got terrain=%r, trajectory %s, kind=%r): it is the standing-reset Cassie3d"
                              % (terrain, "given" if trajectory is not None else "None", kind))

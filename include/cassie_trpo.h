@@ -367,6 +367,21 @@ int CassieEsWidePolicyStep(const double* obs_dev, int n, int obs_dim, int act_di
                            const long long* offsets_dev, float sigma, const unsigned char* alive_dev, const double* low_dev, const double* high_dev,
                            double* env_actions_dev, void* stream);
 
+/* ---- ES at 45 x 10 (csrc/tu_es3d.hip): the same six for Cassie3d's shape, obs_dim 45 and act_dim 10, the one shape they take.
+ * CassieEs3dParamCount is 2858 (32 x 32) and CassieEs3dWideParamCount 23 690 (128 x 128) for (45, 10), 0 for any other shape; the two policy steps
+ * have CassieEsPolicyStep's arguments, contract and return codes with these P.  CassieEsParamCount and CassieEsWideParamCount stay 0 at (45, 10):
+ * the shape lives behind these symbols only.  CassieEsBook and CassieEsGrad serve this shape as they are. */
+int CassieEs3dParamCount(int obs_dim, int act_dim);
+int CassieEs3dPairsPerWorkgroup(void);
+int CassieEs3dPolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* theta_dev, const float* table_dev, long long table_len,
+                         const long long* offsets_dev, float sigma, const unsigned char* alive_dev, const double* low_dev, const double* high_dev,
+                         double* env_actions_dev, void* stream);
+int CassieEs3dWideParamCount(int obs_dim, int act_dim);
+int CassieEs3dWidePairsPerWorkgroup(void);
+int CassieEs3dWidePolicyStep(const double* obs_dev, int n, int obs_dim, int act_dim, const float* theta_dev, const float* table_dev, long long table_len,
+                             const long long* offsets_dev, float sigma, const unsigned char* alive_dev, const double* low_dev, const double* high_dev,
+                             double* env_actions_dev, void* stream);
+
 /* Bookkeeping of one Env.step of the population in one launch, with rew / done as CassieVecStep wrote them:
  *   fitness[i] += alive[i] ? rew[i] : 0;  length[i] += alive[i];  alive[i] &= !done[i]   (alive: one byte, 0 / 1). */
 int CassieEsBook(const double* rew_dev, const unsigned char* done_dev, int n, unsigned char* alive_dev, double* fitness_dev, long long* length_dev, void* stream);

@@ -54,7 +54,12 @@ def main():
         from cassierl_amd.es import make_cassie_es
         if args.envs % 2:
             ap.error("an ES snapshot needs an even --envs (two environments per direction), got %d" % args.envs)
-        algo = make_cassie_es(args.envs, kind=args.kind, control_mode=args.control_mode, device=0, trajectory=default_gait(), seed=args.seed, terrain=terrain,
+        if ck.get("env_family", "cassie2d") == "cassie3d":   # written by train_es.py --env cassie3d: the control mode and gains are the snapshot's
+            cfg = ck["env_config"]
+            env_kw = dict(env="cassie3d", control_mode=cfg["control_mode"], kp=cfg["kp"], kd=cfg["kd"])
+        else:
+            env_kw = dict(kind=args.kind, control_mode=args.control_mode, trajectory=default_gait(), terrain=terrain)
+        algo = make_cassie_es(args.envs, device=0, seed=args.seed, **env_kw,
                               hidden_sizes=tuple(ck.get("hidden_sizes", (32, 32))), table_size=ck["table_size"], table_seed=ck["table_seed"])
         args.deterministic = True
     elif ck.get("algo") == "ddpg":   # a train_ddpg.py snapshot: the deterministic actor mu(s); only the policy is loaded, so the smallest pool will do
