@@ -51,6 +51,8 @@ EXPORTS = [
     "CassieTrpoGae", "CassieTrpoClipGradRows", "CassieTrpoClipGrad", "CassiePgClipGradRows", "CassiePgClipGrad",
     # PPO at the Cassie3d shape, 45 x 10 (include/cassie_trpo.h)
     "CassiePg3dParamCount", "CassiePg3dPolicyStep", "CassiePg3dClipGradRows", "CassiePg3dClipGrad",
+    # PPO's value network, 26 and 45 observations (include/cassie_trpo.h)
+    "CassieVfParamCount", "CassieVfPredict", "CassieVfGae", "CassieVfGradRows", "CassieVfGrad",
     # ES (include/cassie_trpo.h)
     "CassieEsParamCount", "CassieEsPairsPerWorkgroup", "CassieEsPolicyStep", "CassieEsBook", "CassieEsGradRows", "CassieEsGrad",
     "CassieEsWideParamCount", "CassieEsWidePairsPerWorkgroup", "CassieEsWidePolicyStep",

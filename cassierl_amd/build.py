@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "libcassie2d.so")
-UNITS = ["cassie_cabi", "tu_base", "tu_g16", "tu_leg", "tu_leg_seg", "tu_duo", "tu_duo_hf", "tu_hf", "tu_ctrl", "tu_ctrl_g16", "tu_3d", "tu_3d_env", "tu_trpo", "tu_trpo_baseline", "tu_pg", "tu_pg_trpo", "tu_ddpg", "tu_ppo", "tu_sac", "tu_sac3d", "tu_td3", "tu_es", "tu_es_wide", "tu_es3d", "tu_pg3d", "cassie3d_cabi"]
+UNITS = ["cassie_cabi", "tu_base", "tu_g16", "tu_leg", "tu_leg_seg", "tu_duo", "tu_duo_hf", "tu_hf", "tu_ctrl", "tu_ctrl_g16", "tu_3d", "tu_3d_env", "tu_trpo", "tu_trpo_baseline", "tu_pg", "tu_pg_trpo", "tu_ddpg", "tu_ppo", "tu_sac", "tu_sac3d", "tu_td3", "tu_es", "tu_es_wide", "tu_es3d", "tu_pg3d", "tu_vf", "cassie3d_cabi"]
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"] + os.environ.get("CASSIE_HIPCC_FLAGS", "").split()

@@ -6,7 +6,8 @@ statements in this module are the specification, the kernels of csrc/tu_ppo.hip 
   advantages  per environment column of the [T][N] batch, backwards, float64 (gae_advantages; CassieTrpoGae):
                 live = 1 - cut;  delta = r + gamma live V(s') - V(s);  adv = delta + gamma lambda live adv';  returns as TRPO's.
               V is the LinearFeatureBaseline; a path cut at max_path_length is terminal, as for TRPO and VPG.  Centring and the baseline
-              fit are OnPolicy.process's.
+              fit are OnPolicy.process's.  With a value.MLPValueFunction in the baseline slot (make_cassie_ppo(value="mlp")) V is that network,
+              nothing is fitted in process(), and every minibatch step is followed by one Adam step of the value network: value.py.
   loss        of one minibatch of M samples (all ranks together), ratio = exp(ll_new(a) - ll_old(a))  (ppo_loss):
                 L = -(1/M) sum min(ratio adv, clip(ratio, 1 - eps, 1 + eps) adv) - entropy_coeff sum_a (log_std_a + 0.5 log(2 pi e))
   gradient    in closed form (clipped_grad_closed_form; CassieTrpoClipGrad / CassiePgClipGrad evaluate it in one launch):
@@ -26,11 +27,12 @@ import torch
 import torch.distributed as dist
 
 from ._lib import Kernels, available, ptr
-from .adam import FlatAdam
+from .adam import FlatAdam, adam_step_, fused_adam_step_
 from .comm import _world, all_mean_, all_sum_
 from .fisher import AnalyticFisher
 from .policy import GaussianMLPPolicy, _MEAN_ORDER, _two_layer_tanh, add_to_log_std_slot_, flat_grad, flat_params, hidden_sizes_of, set_flat_params
 from .sampler import OnPolicy, broadcast_initial_policy, gaussian_policy_nets, make_cassie_algo
+from .value import MLPValueFunction, ValueKernels, aligned_value_params
 
 
 # --------------------------------------------------------------------------------------------- the torch statements
@@ -208,16 +210,22 @@ class ClipGradKernels(Kernels):
 # --------------------------------------------------------------------------------------------- PPO
 class PPO(FlatAdam, OnPolicy):
     """PPO on OnPolicy's sampler and baseline.  Switches (attributes, default True) that tests set to force the torch path: fused_policy_step,
-    fused_gae (CassieTrpoGae), fused_grad (ClipGradKernels), fused_adam (CassiePgAdam).  last_grad_kind says which gradient ran."""
+    fused_gae (CassieTrpoGae), fused_grad (ClipGradKernels), fused_adam (CassiePgAdam).  last_grad_kind says which gradient ran.
+    baseline: a LinearFeatureBaseline, or a value.MLPValueFunction (recognised by type) -- then fused_value (ValueKernels) is one more switch, fused_gae
+    and fused_adam cover CassieVfGae and the value network's Adam step, last_value_kind says which value path ran, and the value network has its own
+    Adam state (value_adam_t, value_adam_m, value_adam_v) and step size value_learning_rate."""
     ALGO = "ppo"
     CASSIE3D = True   # make_cassie_ppo(..., env="cassie3d"): the 45 x 10 policy on csrc/tu_pg3d.hip and the baseline kernels at 45
 
     def __init__(self, env_step, env_reset, policy, baseline, n_envs, obs_dim, act_map, batch_size=10000, max_path_length=1000, discount=0.99,
                  learning_rate=3e-4, clip_range=0.2, gae_lambda=0.95, epochs=4, minibatch_size=None, entropy_coeff=0.0, beta1=0.9, beta2=0.999,
-                 epsilon=1e-8, seed=1, env_reset_masked=None, env_id0=None):
+                 epsilon=1e-8, seed=1, env_reset_masked=None, env_id0=None, value_learning_rate=1e-3):
         super().__init__(env_step, env_reset, policy, baseline, n_envs, obs_dim, act_map, batch_size=batch_size, max_path_length=max_path_length,
                          discount=discount, seed=seed, env_reset_masked=env_reset_masked, env_id0=env_id0)
         self._adam_init(learning_rate, beta1, beta2, epsilon)
+        self.value_learning_rate = value_learning_rate
+        self.value_adam_t, self.value_adam_m, self.value_adam_v = 0, None, None
+        self.last_value_kind = None
         self.clip_range, self.gae_lambda, self.epochs, self.entropy_coeff = clip_range, gae_lambda, int(epochs), entropy_coeff
         world, n_local = _world(), self.horizon * n_envs
         self.minibatch_size = n_local * world // 4 if minibatch_size is None else int(minibatch_size)
@@ -241,6 +249,8 @@ class PPO(FlatAdam, OnPolicy):
     def _advantages(self, bk, batch, obs, tt):
         """OnPolicy.process's hook with GAE(lambda) advantages: CassieTrpoGae, or gae_advantages on the values of the kernels or of the baseline."""
         T, N = batch["rew"].shape
+        if self.value_kind == "mlp":
+            return self._value_advantages(batch, obs)
         coeffs = self.baseline.coeffs
         self.last_gae_fused = bk is not None and getattr(self, "fused_gae", True)
         if self.last_gae_fused:
@@ -251,6 +261,43 @@ class PPO(FlatAdam, OnPolicy):
         else:
             last_v, values = self.baseline.predict(self.obs.to(obs.dtype), self.path_t), self.baseline.predict(obs, tt).view(T, N)
         return (*gae_advantages(batch["rew"], batch["done"], values, last_v, self.discount, self.gae_lambda), None)
+
+    @property
+    def value_kind(self):
+        return "mlp" if isinstance(self.baseline, MLPValueFunction) else "linear"
+
+    def _load_baseline_coeffs(self, coeffs, dev):
+        if self.value_kind == "linear":   # (the value network has no coefficients: its snapshot entry is None)
+            super()._load_baseline_coeffs(coeffs, dev)
+
+    def _value_advantages(self, batch, obs):
+        """_advantages with the value network: V of every sample and of self.obs (ValueKernels.predict), GAE and the value target y = adv + V
+        (ValueKernels.gae).  V_old and y go into process()'s dictionary for optimize()."""
+        T, N = batch["rew"].shape
+        vf = self.baseline
+        vk = ValueKernels(vf, aligned_value_params(vf), fused=getattr(self, "fused_value", True))
+        self.last_value_kind = vk.kind
+        values = vk.predict(obs).view(T, N)
+        last_v = vk.predict(self.obs.to(obs.dtype).contiguous())
+        self.last_gae_fused = vk.kind == "vf_grad" and getattr(self, "fused_gae", True)
+        returns, adv, y, sums = vk.gae(values, last_v, batch["rew"], batch["done"], self.discount, self.gae_lambda, fused=self.last_gae_fused)
+        self._value_batch = dict(v_old=values.reshape(-1), vtarget=y.reshape(-1))
+        return returns, adv, sums
+
+    def _processed_extras(self):
+        if self.value_kind != "mlp":
+            return {}
+        extras, self._value_batch = self._value_batch, None
+        return extras
+
+    def _value_adam_step(self, theta, g):
+        """One Lasagne Adam step of the value network's flat vector: FlatAdam.adam_step's rule on the second state."""
+        if self.value_adam_m is None:
+            self.value_adam_m, self.value_adam_v = torch.zeros_like(theta), torch.zeros_like(theta)
+        self.value_adam_t += 1
+        fused = getattr(self, "fused_adam", True) and theta.is_cuda and theta.dtype == torch.float32
+        (fused_adam_step_ if fused else adam_step_)(theta, g, self.value_adam_m, self.value_adam_v, self.value_adam_t, self.value_learning_rate, self.beta1,
+                                                    self.beta2, self.epsilon)
 
     def optimize(self, d):
         pol = self.policy
@@ -263,6 +310,12 @@ class PPO(FlatAdam, OnPolicy):
         self.last_grad_kind = ck.kind
         # per minibatch step (loss sum, KL sum, clipped samples, gradient norm), kept on the device and read once behind the loop
         acc = torch.zeros((self.epochs * nmb, 4), dtype=torch.float64, device=obs.device)
+        vk = None
+        if self.value_kind == "mlp":   # the value network's flat vector, updated in place beside the policy's
+            vk = ValueKernels(self.baseline, aligned_value_params(self.baseline), fused=getattr(self, "fused_value", True))
+            vk.set_batch(obs, d["vtarget"])
+            self.last_value_kind = vk.kind
+        vacc = None if vk is None else torch.zeros(self.epochs * nmb, dtype=torch.float64, device=obs.device)   # per minibatch step: sum (V - y)^2 / 2
         self.last_perms = []
         k = 0
         for _ in range(self.epochs):
@@ -275,31 +328,97 @@ class PPO(FlatAdam, OnPolicy):
                 g = all_mean_(g.contiguous(), "gradient_all_reduce")
                 acc[k, 3] = torch.linalg.vector_norm(g, dtype=torch.float64)
                 self.adam_step(theta, g.to(theta.dtype))
+                if vk is not None:   # the value network's step on the same rows
+                    gv, _ = vk.grad(idx, stats_out=vacc[k])
+                    gv = all_mean_(gv.contiguous(), "gradient_all_reduce")
+                    self._value_adam_step(vk.theta, gv.to(vk.theta.dtype))
                 k += 1
         set_flat_params(pol, theta)
         M = float(m * world)
         ent = self.entropy_coeff * float(pol.log_std.numel()) * 0.5 * math.log(2.0 * math.pi * math.e)   # (the log_std part of the bonus is not logged)
         sums = all_sum_(acc[:, :3].contiguous(), "stats_all_reduce")
+        if vk is not None:
+            return self._stats_with_value(vk, d, sums, acc, vacc, M, ent)
         rows = torch.cat([sums, acc[:, 3:]], dim=1).tolist()   # the one read-back
+        return self._policy_stats(rows, M, ent)
+
+    @staticmethod
+    def _policy_stats(rows, M, ent):
         return dict(loss_first=rows[0][0] / M - ent, loss_last=rows[-1][0] / M - ent, mean_kl=sum(r[1] for r in rows) / (M * len(rows)),
                     clip_frac=sum(r[2] for r in rows) / (M * len(rows)), grad_norm=sum(r[3] for r in rows) / len(rows), minibatch_steps=len(rows))
 
+    def _stats_with_value(self, vk, d, sums, acc, vacc, M, ent):
+        """optimize()'s statistics with the value network's: its parameters go back into the module, and the value losses and the sums of the
+        explained variance 1 - Var(y - V_old) / Var(y) (over the batch, all ranks) join the one read-back."""
+        set_flat_params(self.baseline, vk.theta)
+        y = d["vtarget"].double()
+        dv = y - d["v_old"].double()
+        ev = torch.stack([dv.sum(), (dv * dv).sum(), y.sum(), (y * y).sum(), torch.tensor(float(y.numel()), dtype=torch.float64, device=y.device)])
+        extra = all_sum_(torch.cat([vacc, ev]), "stats_all_reduce")
+        K = acc.shape[0]
+        flat = torch.cat([torch.cat([sums, acc[:, 3:]], dim=1).reshape(-1), extra]).tolist()   # the one read-back
+        rows, vl, (s1, s2, t1, t2, cnt) = [flat[4 * i:4 * i + 4] for i in range(K)], flat[4 * K:5 * K], flat[5 * K:]
+        var_d, var_y = s2 / cnt - (s1 / cnt) ** 2, t2 / cnt - (t1 / cnt) ** 2
+        return dict(self._policy_stats(rows, M, ent), value_loss_first=vl[0] / M, value_loss_last=vl[-1] / M,
+                    explained_variance=1.0 - var_d / var_y if var_y > 0.0 else float("nan"))
+
     # ---- snapshot: Sampler's, plus the algorithm, the policy shape, the hyper-parameters, the Adam state and the permutation generator
     def _snapshot_fields(self):
-        return dict(super()._snapshot_fields(), learning_rate=float(self.learning_rate), clip_range=float(self.clip_range), gae_lambda=float(self.gae_lambda),
-                    epochs=int(self.epochs), minibatch_size=int(self.minibatch_size), entropy_coeff=float(self.entropy_coeff), **self._adam_snapshot(),
-                    gen_mb_state=self.gen_mb.get_state())
+        f = dict(super()._snapshot_fields(), learning_rate=float(self.learning_rate), clip_range=float(self.clip_range), gae_lambda=float(self.gae_lambda),
+                 epochs=int(self.epochs), minibatch_size=int(self.minibatch_size), entropy_coeff=float(self.entropy_coeff), **self._adam_snapshot(),
+                 gen_mb_state=self.gen_mb.get_state())
+        if self.value_kind == "mlp":   # (a snapshot without value_kind is a linear-baseline run's: its entries are what they were)
+            cpu = lambda x: None if x is None else x.detach().cpu()
+            f.update(value_kind="mlp", value_hidden=list(self.baseline.hidden_sizes), value_net=flat_params(self.baseline).detach().cpu(),
+                     value_adam_t=int(self.value_adam_t), value_adam_m=cpu(self.value_adam_m), value_adam_v=cpu(self.value_adam_v),
+                     value_learning_rate=float(self.value_learning_rate))
+        return f
 
     def _load_fields(self, ck):
         super()._load_fields(ck)
+        theirs, mine = ck.get("value_kind", "linear"), self.value_kind
+        if theirs != mine:
+            raise ValueError("PPO.load: the snapshot's value function is %r, this run's is %r" % (theirs, mine))
+        if mine == "mlp" and tuple(ck["value_hidden"]) != self.baseline.hidden_sizes:
+            raise ValueError("PPO.load: the snapshot's value network has hidden sizes %r, this run's has %r" % (tuple(ck["value_hidden"]), self.baseline.hidden_sizes))
+        if mine == "mlp" and ck["value_net"].numel() != sum(p.numel() for p in self.baseline.parameters()):   # (another observation width: the other robot's)
+            raise ValueError("PPO.load: the snapshot's value network has %d parameters, this run's has %d"
+                             % (ck["value_net"].numel(), sum(p.numel() for p in self.baseline.parameters())))
         self._adam_load(ck)
         if ck.get("gen_mb_state") is not None:
             self.gen_mb.set_state(ck["gen_mb_state"])
+        if mine == "mlp":
+            dev = next(self.baseline.parameters()).device
+            back = lambda x: None if x is None else x.to(dev)
+            set_flat_params(self.baseline, ck["value_net"].to(dev))
+            self.value_adam_t, self.value_adam_m, self.value_adam_v = int(ck["value_adam_t"]), back(ck["value_adam_m"]), back(ck["value_adam_v"])
+            self.value_learning_rate = float(ck.get("value_learning_rate", self.value_learning_rate))
+
+
+def broadcast_initial_networks(algo):
+    """sampler.broadcast_initial_policy, and rank 0's value network is authoritative too (a collective: every rank must call it)."""
+    broadcast_initial_policy(algo)
+    if algo.value_kind == "mlp" and dist.is_initialized() and dist.get_world_size() > 1:
+        theta = flat_params(algo.baseline)
+        dist.broadcast(theta, 0)
+        set_flat_params(algo.baseline, theta)
+
+
+def policy_and_value_nets(hidden_sizes, init_std, value_hidden):
+    """make_nets with a learned value function: the GaussianMLPPolicy, then -- right after it, so that the seed fixes both -- the MLPValueFunction."""
+    def make(obs_dim, act_dim, dev):
+        pol = GaussianMLPPolicy(obs_dim, act_dim, tuple(hidden_sizes), init_std=init_std).to(dev)
+        return pol, MLPValueFunction(obs_dim, tuple(value_hidden)).to(dev)
+    return make
 
 
 def make_cassie_ppo(n_envs, kind="walk", control_mode="PD", device=0, trajectory=None, seed=1, hidden_sizes=(128, 128), init_std=1.0, terrain=None,
-                    sync_policy=True, **kw):
+                    sync_policy=True, value="linear", value_hidden=(128, 128), value_learning_rate=1e-3, **kw):
     """PPO on the batched MI355X environment; the counterpart of vpg.make_cassie_vpg (same env, terrain and sync_policy rules).  env="cassie3d"
-    (with control_mode and, through **kw, kp / kd) runs it on Cassie3dVecEnv: sampler.make_cassie_algo."""
-    return make_cassie_algo(PPO, gaussian_policy_nets(hidden_sizes, init_std), broadcast_initial_policy, n_envs, kind, control_mode, device, trajectory, seed,
-                            terrain, sync_policy, **kw)
+    (with control_mode and, through **kw, kp / kd) runs it on Cassie3dVecEnv: sampler.make_cassie_algo.  value: "linear" (the LinearFeatureBaseline)
+    or "mlp" (value.MLPValueFunction(obs_dim, value_hidden), trained with value_learning_rate)."""
+    if value not in ("linear", "mlp"):   # (checked before any device is touched)
+        raise ValueError("make_cassie_ppo: value must be 'linear' or 'mlp', got %r" % (value,))
+    nets = gaussian_policy_nets(hidden_sizes, init_std) if value == "linear" else policy_and_value_nets(hidden_sizes, init_std, value_hidden)
+    return make_cassie_algo(PPO, nets, broadcast_initial_networks, n_envs, kind, control_mode, device, trajectory, seed, terrain, sync_policy,
+                            value_learning_rate=value_learning_rate, **kw)

@@ -368,7 +368,11 @@ class OnPolicy(Sampler):
             self.baseline.fit_normal_equations(A, b, bk.ridge_solve if getattr(self, "fused_solve", True) else None)
         else:
             self.baseline.fit(obs, tt, flat(returns))
-        return dict(obs=obs, act=flat(batch["act"]), mean=flat(batch["mean"]), log_std=flat(batch["log_std"]), adv=adv)
+        return dict(obs=obs, act=flat(batch["act"]), mean=flat(batch["mean"]), log_std=flat(batch["log_std"]), adv=adv, **self._processed_extras())
+
+    def _processed_extras(self):
+        """process()'s hook: further entries of the processed batch (PPO with a value network: its value targets); none by default."""
+        return {}
 
     def train_iteration(self):
         from . import rollout as R

@@ -308,6 +308,30 @@ int CassiePg3dClipGrad(const float* obs_dev, int n, int obs_dim, int act_dim, co
                        const float* old_mean_dev, const float* log_std_old, const float* log_std_new, float clip, float scale, float* partial_dev,
                        double* stats_dev, void* stream);
 
+/* ---- value network: PPO's learned V(s) (cassierl_amd/value.py, csrc/tu_vf.hip), the 128 x 128 tanh network of the width-128 policy with ONE
+ * output row -- W1 [128][obs_dim], b1 [128], W2 [128][128], b2 [128], W3 [1][128], b3 [1], float32, row-major as torch.nn.Linear, b1 / W2 / b2 / W3
+ * 16-byte aligned -- for obs_dim 26 (Cassie2d) and 45 (Cassie3d).  Any other shape: CassieVfParamCount is 0 and the launchers return CASSIE_EINVAL;
+ * so does a null pointer, n / m / T <= 0 or a misaligned pointer, before anything is launched or written.  Adam is CassiePgAdam.  Every sum runs
+ * in a fixed order: a call repeats bit for bit. */
+int CassieVfParamCount(int obs_dim);   /* 128 obs_dim + 128 + 128^2 + 128 + 128 + 1, or 0 */
+
+/* value[i] = V(obs[i]) for i < n (obs [n][obs_dim] float32), one launch; rows past n are untouched. */
+int CassieVfPredict(const float* obs_dev, int n, int obs_dim, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                    const float* b3, float* value_dev, void* stream);
+
+/* CassieTrpoGae with the value of every sample READ from values [T][n] (float32, promoted) instead of evaluated, last_value [n] float32 (NULL = 0),
+ * and the value target vtarget[s] = adv[s] + values[s] (the lambda-return) beside returns and adv; partial[(n + 255) / 256][2] = (sum adv, sum adv^2). */
+int CassieVfGae(const float* values_dev, const float* last_value_dev, const double* rew_dev, const unsigned char* cut_dev, int T, int n, double gamma,
+                double lambda, double* returns_dev, double* adv_dev, double* vtarget_dev, double* partial_dev, void* stream);
+
+/* Gradient of the value loss (1 / 2M) sum_i (V(s_i) - target_i)^2 on one minibatch, one launch: the rows idx [m] of the batch (int64, clamped to
+ * [0, n); NULL = rows 0 .. m - 1, m <= n), the forward pass at the GIVEN weights, the cotangent scale (V - target[row]) in registers (scale = 1 / M),
+ * the reverse pass of CassiePgVjp.  target [n] is indexed by batch row.  partial [rows][ParamCount] float32 = [gW1 | gb1 | gW2 | gb2 | gW3 | gb3],
+ * stats [rows] float64 = sum_s (V - target)^2 / 2; rows = CassieVfGradRows(m), one per workgroup; the caller adds the rows. */
+int CassieVfGradRows(int m);
+int CassieVfGrad(const float* obs_dev, int n, int obs_dim, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                 const float* b3, const long long* idx_dev, int m, const float* target_dev, float scale, float* partial_dev, double* stats_dev, void* stream);
+
 /* ---- SAC at 45 x 10: Soft Actor-Critic on Cassie3d (cassierl_amd/sac.py with env="cassie3d", csrc/tu_sac3d.hip, csrc/mlp32_tiles3d.h).  The networks
  * are still the 32 x 32 ReLU networks above: the actor's W1 [32][45], W3 [20][32] (mean rows [0, 10), log_std rows [10, 20)), a critic's W1 [32][45],
  * W2 [32][42].  The contracts of CassieSacPolicyStep, CassieSacCriticGrad, CassieSacActorGrad and CassieSacApply (here CassieSac3dActorApply) for the

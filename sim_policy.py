@@ -49,7 +49,7 @@ def main():
         else:
             env_kw = dict(kind=args.kind, control_mode=args.control_mode, trajectory=default_gait(), terrain=terrain)
         algo = make_cassie_ppo(args.envs, device=0, seed=args.seed, hidden_sizes=tuple(ck.get("hidden_sizes", (128, 128))), batch_size=args.envs,
-                               minibatch_size=args.envs, **env_kw)
+                               minibatch_size=args.envs, value=ck.get("value_kind", "linear"), value_hidden=tuple(ck.get("value_hidden", (128, 128))), **env_kw)
     elif ck.get("algo") == "es":   # a train_es.py snapshot: the unperturbed parameters, rolled out with the mean (the noise table is the snapshot's)
         from cassierl_amd.es import make_cassie_es
         if args.envs % 2:

@@ -30,7 +30,10 @@ def parser():
     ap.add_argument("--epochs", type=int, default=4, help="passes over each rollout")
     ap.add_argument("--minibatch-size", type=int, default=0, help="samples per Adam step over all ranks (0: a quarter of the batch)")
     ap.add_argument("--entropy-coeff", type=float, default=0.0)
-    ap.add_argument("--torch-update", action="store_true", help="force the torch statements (autograd, torch Adam, torch GAE) instead of the kernels: A/B")
+    ap.add_argument("--value", default="linear", choices=["linear", "mlp"], help="the value function: rllab's LinearFeatureBaseline, or a learned tanh MLP (cassierl_amd/value.py)")
+    ap.add_argument("--value-hidden", default="128,128", help="--value mlp: hidden layer widths of the value network")
+    ap.add_argument("--value-learning-rate", type=float, default=1e-3, help="--value mlp: Adam step size of the value network")
+    ap.add_argument("--torch-update", action="store_true", help="force the torch statements (autograd, torch Adam, torch GAE, the value network's too) instead of the kernels: A/B")
     return ap
 
 
@@ -45,9 +48,10 @@ def main():
     algo = make_cassie_ppo(args.envs_per_gpu, kind=args.kind, control_mode=args.control_mode, device=dev, seed=1,
                            hidden_sizes=hidden, init_std=args.init_std, learning_rate=args.learning_rate, clip_range=args.clip_range,
                            gae_lambda=args.gae_lambda, epochs=args.epochs, minibatch_size=args.minibatch_size or None, entropy_coeff=args.entropy_coeff,
-                           batch_size=args.envs_per_gpu * world * args.horizon, terrain=terrain, **env_kw)
+                           batch_size=args.envs_per_gpu * world * args.horizon, terrain=terrain, value=args.value,
+                           value_hidden=tuple(int(x) for x in args.value_hidden.split(",")), value_learning_rate=args.value_learning_rate, **env_kw)
     if args.torch_update:
-        algo.fused_grad = algo.fused_adam = algo.fused_gae = False
+        algo.fused_grad = algo.fused_adam = algo.fused_gae = algo.fused_value = False
     cli.train(algo, args, args.n_itr, rank)
 
 
