@@ -36,8 +36,19 @@ __device__ __forceinline__ void gemm_block(const float* __restrict__ W, int ld, 
   }
 }
 
-// Forward pass of one tile: h1 = tanh(W1 x + b1), h2 = tanh(W2 h1 + b2) (four blocks each); first layer k = 2 s + h
-template <int D>
+// tanh_fast without its cancellation near 0: 1 - 2 / (e + 1) has an ABSOLUTE error of about 1e-7, a relative one of 1e-3 on an activation of 1e-4.
+// Below 1/16 the odd series x - x^3 / 3 + 2 x^5 / 15 (next term 17 x^7 / 315: 3e-9 of tanh at 1/16); from there on tanh_fast, whose relative
+// error is then 3e-6 or less.
+__device__ __forceinline__ float tanh_near0(float x) {
+  const float x2 = x * x;
+  const float p = x2 * __builtin_fmaf(x2, 0.133333333f, -0.333333333f);
+  return __builtin_fabsf(x) < 0.0625f ? __builtin_fmaf(x, p, x) : tanh_fast(x);
+}
+
+// Forward pass of one tile: h1 = tanh(W1 x + b1), h2 = tanh(W2 h1 + b2) (four blocks each); first layer k = 2 s + h.  NEAR0: tanh_near0 for
+// tanh_fast (tu_vf.hip: a value gradient is judged block by block, and gW3 = sum_s w_s H2[:, s] carries H2's RELATIVE error; the policy units
+// keep tanh_fast and their instructions)
+template <int D, bool NEAR0 = false>
 __device__ __forceinline__ void forward_hidden(const Net& th, const float (&xb)[(D + 1) / 2], v16f (&h1)[NB], v16f (&h2)[NB], int c, int h) {
   constexpr int KS1 = (D + 1) / 2;
 #pragma unroll
@@ -50,7 +61,7 @@ __device__ __forceinline__ void forward_hidden(const Net& th, const float (&xb)[
       y = TILE_MFMA(a, xb[s], y);
     }
 #pragma unroll
-    for (int v = 0; v < 16; v++) y[v] = tanh_fast(y[v]);
+    for (int v = 0; v < 16; v++) y[v] = NEAR0 ? tanh_near0(y[v]) : tanh_fast(y[v]);
     h1[ob] = y;
   }
 #pragma unroll
@@ -59,7 +70,7 @@ __device__ __forceinline__ void forward_hidden(const Net& th, const float (&xb)[
 #pragma unroll
     for (int kb = 0; kb < NB; kb++) gemm_block(th.W2, H, 32 * ob, 32 * kb, true, h1[kb], y, c, h);
 #pragma unroll
-    for (int v = 0; v < 16; v++) y[v] = tanh_fast(y[v]);
+    for (int v = 0; v < 16; v++) y[v] = NEAR0 ? tanh_near0(y[v]) : tanh_fast(y[v]);
     h2[ob] = y;
   }
 }

@@ -4,8 +4,9 @@
 //
 // Read tu_pg.hip's and tu_pg3d.hip's headers first: the layout (exact float32 v_mfma_f32_32x32x2_f32, a tile of 32 samples per wavefront,
 // activations in the accumulator layout, four wavefronts exchanging transposed tiles through two LDS slots) is theirs, and the forward pass of the
-// hidden layers is cassie_pg_net.h's forward_hidden<D>.  The output layer is the padded 32-row tile with W3 on row 0: V of sample c leaves it in
-// register 0 of lane (c, 0).  What one output row changes in the reverse pass:
+// hidden layers is cassie_pg_net.h's forward_hidden<D, true>: tanh_near0, the series below 1/16, because gW3 = sum_s w_s H2[:, s] carries the
+// RELATIVE error of H2 and tanh_fast's is 1e-3 on an activation of 1e-4 (tests/test_gpu_value_edges.py, `tiny`).  The output layer is the padded
+// 32-row tile with W3 on row 0: V of sample c leaves it in register 0 of lane (c, 0).  What one output row changes in the reverse pass:
 //
 //   * the cotangent w = scale (V - target) is one number per sample.  It is formed on lane (c, 0), handed to lane (c, 1) by one shuffle and to the
 //     other wavefronts through 32 floats of LDS per tile (scot);
@@ -44,7 +45,7 @@ __global__ void __launch_bounds__(64 * WAVES, 2) predict_kernel(const float* __r
 #pragma unroll
   for (int s = 0; s < KS1; s++) { const int k = 2 * s + h; xb[s] = (valid && k < D) ? obs[(size_t)smp * D + k] : 0.0f; }
   v16f h1[NB], h2[NB];
-  forward_hidden<D>(th, xb, h1, h2, c, h);
+  forward_hidden<D, true>(th, xb, h1, h2, c, h);
   v16f mu = zero16();
   mu[0] = h == 0 ? th.b3[0] : 0.0f;
 #pragma unroll
@@ -62,7 +63,7 @@ __global__ void __launch_bounds__(256) gae_kernel(const float* __restrict__ valu
   double s1 = 0.0, s2 = 0.0;
   if (i < n) {
     double run = last_value ? (double)last_value[i] : 0.0;
-    double v_next = run, a_next = 0.0;
+    double v_next = run, a_next = 0.0, y_next = run;
     for (int tt = T - 1; tt >= 0; tt--) {
       const size_t s = (size_t)tt * n + i;
       const double value = (double)values[s];
@@ -70,9 +71,12 @@ __global__ void __launch_bounds__(256) gae_kernel(const float* __restrict__ valu
       run = r + gamma * run * live;
       const double delta = r + gamma * live * v_next - value;
       const double a = delta + gamma * lambda * live * a_next;
-      returns[s] = run; adv[s] = a; vtarget[s] = a + value;
+      // the value target a + value by the lambda-return's own recurrence, in which `value` does not appear: a + value cancels where |value| is
+      // far above the return (values of 1e4 beside returns of 5 cost it four digits)
+      const double y = r + gamma * live * ((1.0 - lambda) * v_next + lambda * y_next);
+      returns[s] = run; adv[s] = a; vtarget[s] = y;
       s1 += a; s2 += a * a;
-      v_next = value; a_next = a;
+      v_next = value; a_next = a; y_next = y;
     }
   }
   red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2;
@@ -142,7 +146,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) grad_kernel(const float* __rest
 #pragma unroll
     for (int s = 0; s < KS1; s++) { const int kk = 2 * s + h; xb[s] = (valid && kk < D) ? obs[(size_t)row * D + kk] : 0.0f; }
     v16f h1[NB], h2[NB], g2[NB], g1[NB];
-    forward_hidden<D>(th, xb, h1, h2, c, h);
+    forward_hidden<D, true>(th, xb, h1, h2, c, h);
     float w = 0.0f;
     {
       v16f mu = zero16();

@@ -8,7 +8,8 @@ kernels of csrc/tu_vf.hip evaluate them for the 128 x 128 network at 26 and 45 o
   advantages  ppo.gae_advantages on values = V of every sample and last_value = V of the sampler's current observation, both predicted in the
               network's precision and promoted to float64 (CassieVfPredict, CassieVfGae); a cut is terminal, as for the linear baseline.
   target      y = adv + values, the lambda-return, with adv the GAE advantage BEFORE process() centres it; float64, handed to the update in the
-              network's precision.
+              network's precision.  CassieVfGae evaluates the same number by the lambda-return's own recurrence
+              y_t = r_t + gamma live_t ((1 - lambda) v_{t+1} + lambda y_{t+1}), y_T = last_value, which does not cancel where |values| is large.
   loss        of one minibatch of M samples (all ranks together):  value_loss = (1 / 2M) sum (V(s_i) - y_i)^2.   No value clipping.
   gradient    in closed form (value_grad_closed_form; CassieVfGrad evaluates it in one launch): the reverse pass of the network with the
               cotangent scale (V - y), scale = 1 / M.

@@ -320,7 +320,9 @@ int CassieVfPredict(const float* obs_dev, int n, int obs_dim, const float* W1, c
                     const float* b3, float* value_dev, void* stream);
 
 /* CassieTrpoGae with the value of every sample READ from values [T][n] (float32, promoted) instead of evaluated, last_value [n] float32 (NULL = 0),
- * and the value target vtarget[s] = adv[s] + values[s] (the lambda-return) beside returns and adv; partial[(n + 255) / 256][2] = (sum adv, sum adv^2). */
+ * and the value target vtarget[s] = adv[s] + values[s] (the lambda-return, evaluated by its own recurrence y_t = r_t + gamma live_t ((1 - lambda)
+ * v_{t+1} + lambda y_{t+1}), which does not cancel where |values| is far above the return) beside returns and adv; partial[(n + 255) / 256][2] =
+ * (sum adv, sum adv^2). */
 int CassieVfGae(const float* values_dev, const float* last_value_dev, const double* rew_dev, const unsigned char* cut_dev, int T, int n, double gamma,
                 double lambda, double* returns_dev, double* adv_dev, double* vtarget_dev, double* partial_dev, void* stream);
 
