@@ -1,6 +1,6 @@
 // cassie_tiles.h -- the accumulator-layout primitives every matrix-core network kernel of the library is written in, one copy: the tanh policies
 // of both widths (tu_trpo.hip, tu_ppo.hip, cassie_onpolicy.h; cassie_pg_net.h, tu_pg.hip, tu_pg_trpo.hip) and the 32 x 32 ReLU networks
-// (mlp32_tiles.h, tu_ddpg.hip, tu_sac.hip, tu_td3.hip).  tu_es.hip and tu_es_wide.hip take tanh_fast and wave_lds_sync from here.
+// (mlp32_tiles.h, sac_kernels.h, tu_ddpg.hip, tu_sac.hip, tu_sac3d.hip, tu_td3.hip).  tu_es.hip and tu_es_wide.hip take tanh_fast and wave_lds_sync from here.
 //
 // The layout (tu_trpo.hip's header tells why): exact float32 v_mfma_f32_32x32x2_f32, a tile of 32 samples per wavefront, the sample on the lane
 // c = lane & 31, row row_of(v, h) of a 32-row block in register v of the lane half h = lane >> 5.
@@ -94,6 +94,14 @@ constexpr int H = 32;
 constexpr int TP = 36;            // floats per row of a transpose tile (16-byte aligned rows; ds_read_b128 of 16 lanes conflict-free)
 constexpr int WAVES = 4;          // wavefronts per workgroup: one per SIMD
 
+// The actions in the accumulator layout, from A alone.  An action tile has NS = act_slots(A) SLOTS per lane half, registers v < NS, and slot (v, h) is
+// action a = row_of(v, h) where that is < A.  A <= 8: NS = 4 and a = v + 4 h (row_of's first quad).  8 < A <= 12: NS = A - 4, registers 4 .. NS - 1 are
+// rows 8 .. on half 0 and dead rows 12 .. on half 1 (A = 10: six live slots on half 0, actions 0..3, 8, 9, four on half 1, 4..7).  A two-headed
+// output layer (mean [0, A), log_std [A, 2 A)) keeps log_std a in register v + HREG = head_reg(A) of the lane that holds mean a in register v:
+// row_of(v + HREG, h) = row_of(v, h) + 2 HREG for v < HREG, so log_std a sits on image row 2 HREG + a (head_row).
+constexpr int act_slots(int A) { return A <= 8 ? 4 : A - 4; }
+constexpr int head_reg(int A) { return A <= 8 ? 4 : 8; }
+
 // Element `st` (k-step) of the A operand of a product for lane (c, h): see tu_trpo.hip's header for why W[c][row_of(st, h)] is what k-step st
 // of Y = W X needs when X sits in the accumulator layout.
 enum Kind {
@@ -103,17 +111,21 @@ enum Kind {
   K_OUT,     // the actor's W3 [A][32] padded to 32 rows
   K_HIDT,    // W [32][32] transposed (reverse mode)
   K_HIDQT,   // the critic's W2 hidden columns transposed
-  K_ACTIN,   // the critic's W2 action columns: k-step st < 4 sums over action a = st + 4 h
-  K_W3T,     // the actor's W3 transposed: cotangent row a = st + 4 h, st < 4
+  K_ACTIN,   // the critic's W2 action columns: k-step st < NS sums over the actions of slot st, a = row_of(st, h)
+  K_W3T,     // the actor's W3 transposed: cotangent row a = row_of(st, h), st < NS
   K_DA,      // the critic's W2 action columns transposed, padded to 32 rows: dQ/da = W2a' G2
-  K_HEAD,    // a two-headed actor's W3 [2 A][32], rows permuted by head_row and padded to 32 (tu_sac.hip)
-  K_HEADT    // that W3 transposed: cotangent row head_row(row_of(st, h)), st < 8
+  K_HEAD,    // a two-headed actor's W3 [2 A][32], rows permuted by head_row and padded to 32 (sac_kernels.h)
+  K_HEADT    // that W3 transposed: cotangent row head_row(row_of(st, h)), st < 2 HREG
 };
 // row of a two-headed output layer (mean [0, A), log_std [A, 2 A)) that image row i of the output tile holds: mean a on image row a, log_std a on
-// image row 8 + a (a < A <= 8), -1 for a padding row
-template <int A> __device__ __forceinline__ int head_row(int i) { return i < 8 ? (i < A ? i : -1) : (i < 16 && i - 8 < A ? A + i - 8 : -1); }
+// image row 2 HREG + a (8 + a for A <= 8, 16 + a above), -1 for a padding row
+template <int A> __device__ __forceinline__ int head_row(int i) {
+  constexpr int R = 2 * head_reg(A);
+  static_assert(A <= 12, "mean a in a register v < NS <= HREG, log_std a in v + HREG < 16");
+  return i < A ? i : (i >= R && i - R < A ? A + i - R : -1);
+}
 template <int D, int A> __device__ __forceinline__ float wel(int kind, const float* __restrict__ W, int st, int c, int h) {
-  constexpr int HA = H + A, KS1 = (D + 1) / 2;
+  constexpr int HA = H + A, KS1 = (D + 1) / 2, NS = act_slots(A);
   const int r = row_of(st, h);
   switch (kind) {
     case K_FIRST: { const int k = 2 * st + h; return (st < KS1 && k < D) ? W[c * D + k] : 0.0f; }
@@ -122,10 +134,10 @@ template <int D, int A> __device__ __forceinline__ float wel(int kind, const flo
     case K_OUT: return c < A ? W[c * H + r] : 0.0f;
     case K_HIDT: return W[r * H + c];
     case K_HIDQT: return W[r * HA + c];
-    case K_ACTIN: { const int a = st + 4 * h; return (st < 4 && a < A) ? W[c * HA + H + a] : 0.0f; }
-    case K_W3T: { const int a = st + 4 * h; return (st < 4 && a < A) ? W[a * H + c] : 0.0f; }
+    case K_ACTIN: return (st < NS && r < A) ? W[c * HA + H + r] : 0.0f;
+    case K_W3T: return (st < NS && r < A) ? W[r * H + c] : 0.0f;
     case K_HEAD: { const int o = head_row<A>(c); return o >= 0 ? W[o * H + r] : 0.0f; }
-    case K_HEADT: { const int o = st < 8 ? head_row<A>(r) : -1; return o >= 0 ? W[o * H + c] : 0.0f; }
+    case K_HEADT: { const int o = st < 2 * head_reg(A) ? head_row<A>(r) : -1; return o >= 0 ? W[o * H + c] : 0.0f; }
     default: return c < A ? W[r * HA + H + c] : 0.0f;   // K_DA
   }
 }
@@ -145,9 +157,9 @@ template <int D, int A, int NG> __device__ __forceinline__ void fill_images(floa
     }
   }
 }
-__device__ __forceinline__ void aop(const float4 (*wimg)[64], int q0, int lane, float (&a)[16]) {   // the 16 k-steps of a product
+template <int NQ = 4> __device__ __forceinline__ void aop(const float4 (*wimg)[64], int q0, int lane, float (&a)[4 * NQ]) {   // the k-steps of a product: 16, or NQ quads
 #pragma unroll
-  for (int q = 0; q < 4; q++) { const float4 w = wimg[q0 + q][lane]; a[4 * q] = w.x; a[4 * q + 1] = w.y; a[4 * q + 2] = w.z; a[4 * q + 3] = w.w; }
+  for (int q = 0; q < NQ; q++) { const float4 w = wimg[q0 + q][lane]; a[4 * q] = w.x; a[4 * q + 1] = w.y; a[4 * q + 2] = w.z; a[4 * q + 3] = w.w; }
 }
 __device__ __forceinline__ void put(float* t, const v16f& x, int c, int h) {   // accumulator layout -> [row][sample] image
 #pragma unroll

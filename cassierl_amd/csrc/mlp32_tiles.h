@@ -1,7 +1,9 @@
-// mlp32_tiles.h -- the device code of the kernels of the 32 x 32 ReLU networks, one copy (tu_ddpg.hip, tu_sac.hip, tu_td3.hip keep what is their
-// own: the heads of their policies, their target action, their statistics and their entry points).  In the order of this file:
-//   * the shapes of a parameter row (Shape), the rule of the actor's output rows (out_row, out_bias) and the images of a network in LDS (LA_*, LQ_*);
-//   * the gather of a tile's operands from the pool through the batch's index (Tile, gather, action_quad);
+// mlp32_tiles.h -- the device code of the kernels of the 32 x 32 ReLU networks, one copy for every shape (D observations, A actions) the family is
+// built for: 26 x 6, 26 x 7, 17 x 6, 17 x 7 and Cassie3d's 45 x 10 (tu_ddpg.hip, tu_sac.hip + tu_sac3d.hip through sac_kernels.h, tu_td3.hip keep
+// what is their own: the heads of their policies, their target action, their statistics and their entry points).  In the order of this file:
+//   * the shapes of a parameter row, the operand counts that follow from D and A and the images of a network in LDS (Shape: KS1, NQ1, NB1, NS,
+//     HREG, LA_*, LQ_*), the rule of the actor's output rows (out_row, out_bias);
+//   * the gather of a tile's operands from the pool through the batch's index (Tile, gather, action_slots);
 //   * forward passes: two_layers, add_action, q_head, actor_forward, w3_row, critic_forward;
 //   * the live critic's tile pass and its row of partial sums (CriticAcc, critic_step, critic_row) and the twin-critic kernel (twin_critic_grad);
 //   * the actor's reverse pass and its row of partial sums (ActorAcc, actor_reverse, actor_row);
@@ -9,6 +11,19 @@
 //   * the Adam step and soft target update (column_sum, entry_of, adam_entry, apply_rows, Offsets).
 // The layout is tu_trpo.hip's (read its header first).  The accumulator-layout primitives, the A-operand images of every matrix product (laid
 // out once per workgroup in LDS) and the per-wavefront LDS transposes are cassie_tiles.h's, shared with the tanh policies.
+//
+// No function here knows a robot: what differs between the shapes follows from D and A (Shape; cassie_tiles.h: act_slots, head_reg).
+//   * The actions.  An action tile has NS slots per lane half, registers v < NS, slot (v, h) = action row_of(v, h) where that is < A: four slots
+//     (a = v + 4 h) up to eight actions, A - 4 above (45 x 10: six, of which 4 and 5 of half 1 are rows 12, 13, dead).  The noise and the pool's
+//     action are loaded into the slots (action_slots), the merge layer takes the action as NS k-steps, k-step v carrying slot v of both halves
+//     (K_ACTIN; six k-steps are two image quads of which the second is half padding), dQ/da comes out of K_DA in the same slots.  A two-headed
+//     output layer keeps log_std a in register v + HREG of the lane that holds mean a in register v: the sample, log pi and both cotangents need
+//     no data movement.  Its reverse pass runs over the 2 HREG k-steps that can hold a cotangent (K_HEADT, HREG / 2 quads; at HREG = 8 that is the
+//     whole tile: four zero k-steps are cheaper than a special case).
+//   * [obs | 1] is D + 1 columns.  The first layer has KS1 = (D + 1) / 2 k-steps in NQ1 image quads.  [gW1 | gb1] of a network is NB1 accumulator
+//     tiles, columns 32 b .. 32 b + 31 (column D is gb1, the columns behind it are fed zeros), and the transposed observations exist once per
+//     column block (Tile::xt).  At 45 observations both blocks are fed from ONE read of the G1 image: the registers are there
+//     (profiles/offpolicy_shape_dedup_kernel_resources.txt), unlike in the width-128 kernel of tu_pg3d.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -19,12 +34,13 @@
 namespace cassie_mlp32 {
 
 using namespace cassie_tiles;
-using namespace cassie_tiles::w32;   // H, TP, WAVES, Kind, wel, Grp, fill_images, aop, put, get
+using namespace cassie_tiles::w32;   // H, TP, WAVES, Kind, wel, Grp, fill_images, aop, put, get, act_slots, head_reg
 
 constexpr int MAX_BLOCKS = 256;   // one workgroup per CU; one partial row per workgroup
 
-// NOUT: rows of the actor's output layer (A, or 2 A with the two heads of tu_sac.hip)
+// NOUT: rows of the actor's output layer (A, or 2 A with the two heads of sac_kernels.h)
 template <int D, int A, int NOUT = A> struct Shape {
+  static_assert(D >= 1 && A >= 1 && A <= 12, "the action slots: registers v < NS <= 8 of the two lane halves are rows 0 .. 15 (cassie_tiles.h: act_slots)");
   static constexpr int HA = H + A;   // row length of the critic's merge layer
   // actor row  [W1 | b1 | W2 | b2 | W3 | b3]
   static constexpr int NPA = H * D + H + H * H + H + NOUT * H + NOUT;
@@ -32,6 +48,16 @@ template <int D, int A, int NOUT = A> struct Shape {
   // critic row [W1 | b1 | W2 | b2 | W3 | b3]
   static constexpr int NPQ = H * D + H + H * HA + H + H + 1;
   static constexpr int Q_W1 = 0, Q_B1 = H * D, Q_W2 = Q_B1 + H, Q_B2 = Q_W2 + H * HA, Q_W3 = Q_B2 + H, Q_B3 = Q_W3 + H;
+  // operands
+  static constexpr int KS1 = (D + 1) / 2;                  // k-steps of the first layer, two observations each
+  static constexpr int NQ1 = D < 32 ? 4 : (KS1 + 3) / 4;   // image quads of W1: one product's four below 32 observations, whole quads of k-steps above
+  static constexpr int NB1 = (D + 32) / 32;                // column blocks of [obs | 1]
+  static constexpr int NS = act_slots(A), HREG = head_reg(A);
+  static constexpr int NQA = (NS + 3) / 4, NQH = HREG / 2;   // image quads of K_ACTIN / K_W3T, and of K_HEADT
+  // A network's images in LDS, counted from its first one: an actor's W1 NQ1, W2 4, W3 4; a critic's W1 NQ1, W2 4, action NQA and then what the
+  // kernel adds (critic_step: W2' 4).  Its rows of sbias: an actor's b1 b2 b3, a critic's b1 b2 W3.
+  enum { LA_W1 = 0, LA_W2 = NQ1, LA_W3 = LA_W2 + 4, LA_N = LA_W3 + 4 };
+  enum { LQ_W1 = 0, LQ_W2 = NQ1, LQ_A = LQ_W2 + 4, LQ_FWD = LQ_A + NQA, LQ_W2T = LQ_FWD, LQ_N = LQ_W2T + 4 };
 };
 
 struct NetRW { float *W1, *b1, *W2, *b2, *W3, *b3; };
@@ -46,11 +72,6 @@ template <int A, int KOUT> __device__ __forceinline__ int out_row(int i) {
 }
 template <int A, int KOUT> __device__ __forceinline__ float out_bias(const float* b3, int i) { const int r = out_row<A, KOUT>(i); return r >= 0 ? b3[r] : 0.0f; }
 
-// A network's images in LDS, counted from its first one: an actor's W1 4, W2 4, W3 4; a critic's W1 4, W2 4, action 1 and then what the kernel
-// adds (critic_step: W2' 4).  Its rows of sbias: an actor's b1 b2 b3, a critic's b1 b2 W3.
-enum { LA_W1 = 0, LA_W2 = 4, LA_W3 = 8, LA_N = 12 };
-enum { LQ_W1 = 0, LQ_W2 = 4, LQ_A = 8, LQ_FWD = 9, LQ_W2T = 9, LQ_N = 13 };
-
 __device__ __forceinline__ void relu16(v16f& x) {
 #pragma unroll
   for (int v = 0; v < 16; v++) x[v] = x[v] > 0.0f ? x[v] : 0.0f;
@@ -60,37 +81,42 @@ __device__ __forceinline__ long long clamp_row(long long i, long long cap) { ret
 // ---- the operands of a tile (samples 32 tl .. 32 tl + 31 of the batch), every per-sample row gathered from the pool through the batch's
 // index, clamped to the pool's capacity; zeros past the batch's end
 template <int D, int A> struct Tile {
-  static constexpr int KS1 = (D + 1) / 2;
+  typedef Shape<D, A> S;
   int smp;                  // the lane's sample, and whether the batch has it
   bool valid;
-  float xb[KS1], xt[16];    // the observation as the first layer's operand; transposed (feature on the lane, column D = ones) for the parameter gradients
-  float xn[KS1], ab[4], at[16], rew, live;   // ALL: next observation, action as the merge layer's operand and transposed, reward, 1 - terminal
+  float xb[S::KS1], xt[S::NB1][16];   // the observation as the first layer's operand; transposed per column block (feature 32 b + c on the lane, column D = ones)
+  float xn[S::KS1], ab[S::NS], at[16], rew, live;   // ALL: next observation, action in the slots and transposed, reward, 1 - terminal
 };
-// a quad of the lane's action components a = v + 4 h from row `row` of an [.][A] array: the pool's actions, or noise indexed by the batch position
-template <int A> __device__ __forceinline__ void action_quad(const float* __restrict__ p, size_t row, bool valid, int h, float (&q)[4]) {
+// the lane's action slots from row `row` of an [.][A] array: the pool's actions, or noise indexed by the batch position; zeros in the dead slots
+template <int A> __device__ __forceinline__ void action_slots(const float* __restrict__ p, size_t row, bool valid, int h, float (&q)[act_slots(A)]) {
 #pragma unroll
-  for (int v = 0; v < 4; v++) q[v] = (valid && v + 4 * h < A) ? p[row * A + v + 4 * h] : 0.0f;
+  for (int v = 0; v < act_slots(A); v++) { const int a = row_of(v, h); q[v] = (valid && a < A) ? p[row * A + a] : 0.0f; }
 }
 // ALL = false: smp, valid, xb, xt (the actor kernels); true: everything (the critic kernels)
 template <bool ALL, int D, int A> __device__ __forceinline__ void gather(const Pool& pool, const long long* __restrict__ idx, int n, int tl, int c, int h, Tile<D, A>& t) {
+  typedef Shape<D, A> S;
   const int s0 = tl * 32;
   t.smp = s0 + c;
   t.valid = t.smp < n;
   const long long gi = t.valid ? clamp_row(idx[t.smp], pool.cap) : 0;
 #pragma unroll
-  for (int s = 0; s < (D + 1) / 2; s++) {
+  for (int s = 0; s < S::KS1; s++) {
     const int k = 2 * s + h;
     const bool on = t.valid && k < D;
     t.xb[s] = on ? pool.obs[gi * D + k] : 0.0f;
     if constexpr (ALL) t.xn[s] = on ? pool.nobs[gi * D + k] : 0.0f;
   }
-  if constexpr (ALL) action_quad<A>(pool.act, gi, t.valid, h, t.ab);
+  if constexpr (ALL) action_slots<A>(pool.act, gi, t.valid, h, t.ab);
 #pragma unroll
   for (int s = 0; s < 16; s++) {
     const int sm = s0 + 16 * h + s;
     const bool on = sm < n;
     const long long gs = on ? clamp_row(idx[sm], pool.cap) : 0;
-    t.xt[s] = c < D ? (on ? pool.obs[gs * D + c] : 0.0f) : (c == D ? 1.0f : 0.0f);
+#pragma unroll
+    for (int b = 0; b < S::NB1; b++) {
+      const int cc = 32 * b + c;
+      t.xt[b][s] = cc < D ? (on ? pool.obs[gs * D + cc] : 0.0f) : (cc == D ? 1.0f : 0.0f);
+    }
     if constexpr (ALL) t.at[s] = (c < A && on) ? pool.act[gs * A + c] : 0.0f;
   }
   if constexpr (ALL) { t.rew = t.valid ? pool.rew[gi] : 0.0f; t.live = t.valid ? 1.0f - pool.term[gi] : 0.0f; }
@@ -99,23 +125,27 @@ template <bool ALL, int D, int A> __device__ __forceinline__ void gather(const P
 // ---- forward passes
 // hidden layers of a network on the first-layer operand xb: h1 = relu(W1 x + b1) and z2 = W2 h1 + b2 (not yet rectified: the critic adds
 // its action columns first)
-template <int KS1> __device__ __forceinline__ void two_layers(const float4 (*wimg)[64], int qW1, int qW2, const float* sb1, const float* sb2, const float (&xb)[KS1],
-                                                              int lane, int h, v16f& h1, v16f& z2) {
-  float aw[16];
+template <int D, int A> __device__ __forceinline__ void two_layers(const float4 (*wimg)[64], int qW1, int qW2, const float* sb1, const float* sb2,
+                                                                   const float (&xb)[Shape<D, A>::KS1], int lane, int h, v16f& h1, v16f& z2) {
+  typedef Shape<D, A> S;
+  float aw1[4 * S::NQ1], aw[16];
   h1 = bias_tile(sb1, h);
-  aop(wimg, qW1, lane, aw);
+  aop<S::NQ1>(wimg, qW1, lane, aw1);
 #pragma unroll
-  for (int s = 0; s < KS1; s++) h1 = TILE_MFMA(aw[s], xb[s], h1);
+  for (int s = 0; s < S::KS1; s++) h1 = TILE_MFMA(aw1[s], xb[s], h1);
   relu16(h1);
   z2 = bias_tile(sb2, h);
   aop(wimg, qW2, lane, aw);
 #pragma unroll
   for (int v = 0; v < 16; v++) z2 = TILE_MFMA(aw[v], h1[v], z2);
 }
-// + W2[:, 32:] a for the action a = v + 4 h in register v < 4 (one quad of k-steps)
-__device__ __forceinline__ void add_action(const float4 (*wimg)[64], int qA, int lane, const float (&ab)[4], v16f& z2) {
-  const float4 w = wimg[qA][lane];
-  z2 = TILE_MFMA(w.x, ab[0], z2); z2 = TILE_MFMA(w.y, ab[1], z2); z2 = TILE_MFMA(w.z, ab[2], z2); z2 = TILE_MFMA(w.w, ab[3], z2);
+// + W2[:, 32:] a for the action in the slots: NS k-steps
+template <int A> __device__ __forceinline__ void add_action(const float4 (*wimg)[64], int qA, int lane, const float (&ab)[act_slots(A)], v16f& z2) {
+  constexpr int NS = act_slots(A), NQA = (NS + 3) / 4;
+  float aw[4 * NQA];
+  aop<NQA>(wimg, qA, lane, aw);
+#pragma unroll
+  for (int v = 0; v < NS; v++) z2 = TILE_MFMA(aw[v], ab[v], z2);
 }
 // q = b3 + W3 . h2 for the sample of this lane (both halves of the wavefront hold the result)
 __device__ __forceinline__ float q_head(const float (&w3)[16], float b3, const v16f& h2) {
@@ -127,13 +157,14 @@ __device__ __forceinline__ float q_head(const float (&w3)[16], float b3, const v
 }
 // the actor whose images start at q0 (LA_*) and whose rows are sb[0 .. 2]: hidden activations a1, a2 and the output layer's pre-activation z3
 // on the image rows of its Kind
-template <int KS1> __device__ __forceinline__ void actor_forward(const float4 (*wimg)[64], int q0, const float (*sb)[32], const float (&xb)[KS1], int lane, int h,
-                                                                 v16f& a1, v16f& a2, v16f& z3) {
-  two_layers<KS1>(wimg, q0 + LA_W1, q0 + LA_W2, sb[0], sb[1], xb, lane, h, a1, a2);
+template <int D, int A> __device__ __forceinline__ void actor_forward(const float4 (*wimg)[64], int q0, const float (*sb)[32], const float (&xb)[Shape<D, A>::KS1], int lane,
+                                                                      int h, v16f& a1, v16f& a2, v16f& z3) {
+  typedef Shape<D, A> S;
+  two_layers<D, A>(wimg, q0 + S::LA_W1, q0 + S::LA_W2, sb[0], sb[1], xb, lane, h, a1, a2);
   relu16(a2);
   float aw[16];
   z3 = bias_tile(sb[2], h);
-  aop(wimg, q0 + LA_W3, lane, aw);
+  aop(wimg, q0 + S::LA_W3, lane, aw);
 #pragma unroll
   for (int v = 0; v < 16; v++) z3 = TILE_MFMA(aw[v], a2[v], z3);
 }
@@ -145,10 +176,12 @@ __device__ __forceinline__ void w3_row(const float* sw3, int h, float (&w3)[16])
 }
 // Q(x, a) of the critic whose images start at q0 (LQ_W1, LQ_W2, LQ_A) and whose rows b1, b2 are sb[0], sb[1], with W3 in w3 (w3_row); h1 and
 // h2 are its hidden activations
-template <int KS1> __device__ __forceinline__ float critic_forward(const float4 (*wimg)[64], int q0, const float (*sb)[32], const float (&w3)[16], float b3,
-                                                                   const float (&xb)[KS1], const float (&ab)[4], int lane, int h, v16f& h1, v16f& h2) {
-  two_layers<KS1>(wimg, q0 + LQ_W1, q0 + LQ_W2, sb[0], sb[1], xb, lane, h, h1, h2);
-  add_action(wimg, q0 + LQ_A, lane, ab, h2);
+template <int D, int A> __device__ __forceinline__ float critic_forward(const float4 (*wimg)[64], int q0, const float (*sb)[32], const float (&w3)[16], float b3,
+                                                                        const float (&xb)[Shape<D, A>::KS1], const float (&ab)[Shape<D, A>::NS], int lane, int h, v16f& h1,
+                                                                        v16f& h2) {
+  typedef Shape<D, A> S;
+  two_layers<D, A>(wimg, q0 + S::LQ_W1, q0 + S::LQ_W2, sb[0], sb[1], xb, lane, h, h1, h2);
+  add_action<A>(wimg, q0 + S::LQ_A, lane, ab, h2);
   relu16(h2);
   return q_head(w3, b3, h2);
 }
@@ -157,24 +190,40 @@ template <int KS1> __device__ __forceinline__ float critic_forward(const float4 
 template <int NROW> __device__ __forceinline__ void reduce_rows(const float* red, float* __restrict__ out) {
   for (int i = threadIdx.x; i < NROW; i += 64 * WAVES) out[i] = ((red[i] + red[NROW + i]) + red[2 * NROW + i]) + red[3 * NROW + i];
 }
+// the transpose tiles of a workgroup, which its reduction re-uses for the wavefronts' rows of NROW floats: the larger of the two (with 2 A output
+// rows at 26 observations, and at 45 observations, the four rows are longer than the tiles)
+template <int NROW> constexpr int tilemem_floats() { return WAVES * 2 * 32 * TP > WAVES * NROW ? WAVES * 2 * 32 * TP : WAVES * NROW; }
+// [gW1 | gb1] of register v (row r) into a wavefront's row: column 32 b + c of block b
+template <int D, int NB1> __device__ __forceinline__ void first_layer_row(const v16f (&g)[NB1], int v, int r, float* gW1, float* gb1, int c) {
+#pragma unroll
+  for (int b = 0; b < NB1; b++) {
+    const int cc = 32 * b + c;
+    if (cc < D) gW1[r * D + cc] = g[b][v];
+    if (cc == D) gb1[r] = g[b][v];
+  }
+}
 
 // ---- the live critic on a tile and its row of partial sums [gW1 | gb1 | gW2 | gb2 | gW3 | gb3 | sum e^2 | sum Q]
-struct CriticAcc { v16f gW1, gW2, gW2a; float gW3[16]; float gb2, gb3, sse, sq; };
-__device__ __forceinline__ void zero(CriticAcc& a) {
+template <int NB1> struct CriticAcc { v16f gW1[NB1], gW2, gW2a; float gW3[16]; float gb2, gb3, sse, sq; };
+template <int NB1> __device__ __forceinline__ void zero(CriticAcc<NB1>& a) {
 #pragma unroll
-  for (int v = 0; v < 16; v++) { a.gW1[v] = 0.0f; a.gW2[v] = 0.0f; a.gW2a[v] = 0.0f; a.gW3[v] = 0.0f; }
+  for (int b = 0; b < NB1; b++) a.gW1[b] = zero16();
+  a.gW2 = zero16(); a.gW2a = zero16();
+#pragma unroll
+  for (int v = 0; v < 16; v++) a.gW3[v] = 0.0f;
   a.gb2 = a.gb3 = a.sse = a.sq = 0.0f;
 }
 // e = Q(s, a) - y of the critic at images q0 (LQ_*, with W2' at LQ_W2T) and rows sb[0 .. 2], and the gradient of sum e^2 in reverse mode:
 // G2 = (W3' dq) o (h2 > 0), G1 = (W2h' G2) o (h1 > 0), then the parameter gradients -- products over the SAMPLE index, operands transposed
-// through the wavefront's LDS tiles t0, t1
+// through the wavefront's LDS tiles t0, t1; one read of the G1 image feeds every column block of [gW1 | gb1]
 template <int D, int A>
 __device__ __forceinline__ void critic_step(const float4 (*wimg)[64], int q0, const float (*sb)[32], float b3, const Tile<D, A>& t, float y, int lane, int c, int h,
-                                            float* t0, float* t1, CriticAcc& acc) {
+                                            float* t0, float* t1, CriticAcc<Shape<D, A>::NB1>& acc) {
+  typedef Shape<D, A> S;
   v16f c1, c2;
   float w3a[16];
   w3_row(sb[2], h, w3a);
-  const float qv = critic_forward(wimg, q0, sb, w3a, b3, t.xb, t.ab, lane, h, c1, c2);
+  const float qv = critic_forward<D, A>(wimg, q0, sb, w3a, b3, t.xb, t.ab, lane, h, c1, c2);
   const float e = t.valid ? qv - y : 0.0f, dq = 2.0f * e;
   if (h == 0 && t.valid) { acc.sse += e * e; acc.sq += qv; acc.gb3 += dq; }
   v16f g2, g1;
@@ -185,7 +234,7 @@ __device__ __forceinline__ void critic_step(const float4 (*wimg)[64], int q0, co
     g1[v] = 0.0f;
   }
   float aw[16], ta_[16], tb_[16];
-  aop(wimg, q0 + LQ_W2T, lane, aw);
+  aop(wimg, q0 + S::LQ_W2T, lane, aw);
 #pragma unroll
   for (int v = 0; v < 16; v++) g1 = TILE_MFMA(aw[v], g2[v], g1);
 #pragma unroll
@@ -201,10 +250,13 @@ __device__ __forceinline__ void critic_step(const float4 (*wimg)[64], int q0, co
   get(t0, ta_, c, h);
   wave_lds_sync();
 #pragma unroll
-  for (int s = 0; s < 16; s++) acc.gW1 = TILE_MFMA(ta_[s], t.xt[s], acc.gW1);
+  for (int s = 0; s < 16; s++) {
+#pragma unroll
+    for (int b = 0; b < S::NB1; b++) acc.gW1[b] = TILE_MFMA(ta_[s], t.xt[b][s], acc.gW1[b]);
+  }
 }
 // this wavefront's row of a critic into LDS
-template <int D, int A> __device__ __forceinline__ void critic_row(CriticAcc& a, float* red, int lane, int c, int h) {
+template <int D, int A> __device__ __forceinline__ void critic_row(CriticAcc<Shape<D, A>::NB1>& a, float* red, int lane, int c, int h) {
   typedef Shape<D, A> S;
 #pragma unroll
   for (int v = 0; v < 16; v++) {
@@ -219,30 +271,28 @@ template <int D, int A> __device__ __forceinline__ void critic_row(CriticAcc& a,
     const int r = row_of(v, h);
     red[S::Q_W2 + r * S::HA + c] = a.gW2[v];
     if (c < A) red[S::Q_W2 + r * S::HA + H + c] = a.gW2a[v];
-    if (c < D) red[S::Q_W1 + r * D + c] = a.gW1[v];
-    if (c == D) red[S::Q_B1 + r] = a.gW1[v];
+    first_layer_row<D>(a.gW1, v, r, red + S::Q_W1, red + S::Q_B1, c);
     if (c == 0) red[S::Q_W3 + r] = a.gW3[v];
   }
   if (h == 0) red[S::Q_B2 + c] = a.gb2;
   if (lane == 0) { red[S::Q_B3] = a.gb3; red[S::NPQ] = a.sse; red[S::NPQ + 1] = a.sq; }
 }
 
-// ---- the twin-critic kernel (tu_sac.hip's and tu_td3.hip's critic_grad_kernel).  Per sample b (pool row i = idx[b]):
+// ---- the twin-critic kernel (sac_kernels.h's and tu_td3.hip's critic_grad_kernel).  Per sample b (pool row i = idx[b]):
 //   y = r_i + (1 - terminal_i) gamma (min(Q1', Q2')(s'_i, a') - sub),  e_k = Q_k(s_i, a_i) - y,
 // and the gradient of sum_b e_k^2 with respect to live critic k; the two live critics run one after the other on the same registers.  Block k
 // of partial: [rows][gW1 | gb1 | gW2 | gb2 | gW3 | gb3 | sum e_k^2 | sum Q_k], CassieDdpgApply's row format.
 // `pi` is the network that gives the target action, its output image of Kind KOUT.  target(wimg, sb, xn, en, lane, h, an) runs it (images at
-// TC_PI, rows sb[0 .. 2]) on the next observation xn with the noise en of the batch position, leaves the action a' in an (0 for a >= A) and
-// returns `sub`.
-enum { TC_PI = 0, TC_T1 = LA_N, TC_T2 = TC_T1 + LQ_FWD, TC_Q1 = TC_T2 + LQ_FWD, TC_Q2 = TC_Q1 + LQ_N, TC_N = TC_Q2 + LQ_N };
+// TC_PI, rows sb[0 .. 2]) on the next observation xn with the noise en of the batch position in the slots, leaves the action a' in the slots of an
+// (0 in the dead ones) and returns `sub`.
+constexpr int TC_PI = 0;
 template <int D, int A, int KOUT, class Target>
 __device__ __forceinline__ void twin_critic_grad(const Pool& pool, const long long* __restrict__ idx, int n, const Net& pi, const Net& tq1, const Net& tq2, const Net& q1,
                                                  const Net& q2, const float* __restrict__ eps_next, float gamma, float* __restrict__ partial, Target target) {
   typedef Shape<D, A> S;
-  static_assert(D < 32 && A <= 8, "a column of ones next to the observations; the action rows in registers 0..3 (a second head: 4..7) of the two lane halves");
-  constexpr int KS1 = (D + 1) / 2, NROW = S::NPQ + 2;
-  static_assert(WAVES * NROW <= WAVES * 2 * 32 * TP, "the workgroup's reduction re-uses the transpose tiles");
-  __shared__ alignas(16) float tilemem[WAVES * 2 * 32 * TP];
+  enum { TC_T1 = S::LA_N, TC_T2 = TC_T1 + S::LQ_FWD, TC_Q1 = TC_T2 + S::LQ_FWD, TC_Q2 = TC_Q1 + S::LQ_N, TC_N = TC_Q2 + S::LQ_N };
+  constexpr int NROW = S::NPQ + 2, NQ1 = S::NQ1, NQA = S::NQA;
+  __shared__ alignas(16) float tilemem[tilemem_floats<NROW>()];
   __shared__ alignas(16) float sbias[15][32];   // pi b1 b2 b3;  target critics b1 b2 W3 each;  live critics b1 b2 W3 each
   __shared__ float4 wimg[TC_N][64];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, h = lane >> 5;
@@ -254,34 +304,36 @@ __device__ __forceinline__ void twin_critic_grad(const Pool& pool, const long lo
     sbias[12][tid] = q2.b1[tid]; sbias[13][tid] = q2.b2[tid]; sbias[14][tid] = q2.W3[tid];
   }
   {
-    const Grp g[17] = {{K_FIRST, pi.W1, TC_PI + LA_W1, 4}, {K_HID, pi.W2, TC_PI + LA_W2, 4}, {KOUT, pi.W3, TC_PI + LA_W3, 4},
-                       {K_FIRST, tq1.W1, TC_T1 + LQ_W1, 4}, {K_HIDQ, tq1.W2, TC_T1 + LQ_W2, 4}, {K_ACTIN, tq1.W2, TC_T1 + LQ_A, 1},
-                       {K_FIRST, tq2.W1, TC_T2 + LQ_W1, 4}, {K_HIDQ, tq2.W2, TC_T2 + LQ_W2, 4}, {K_ACTIN, tq2.W2, TC_T2 + LQ_A, 1},
-                       {K_FIRST, q1.W1, TC_Q1 + LQ_W1, 4}, {K_HIDQ, q1.W2, TC_Q1 + LQ_W2, 4}, {K_ACTIN, q1.W2, TC_Q1 + LQ_A, 1}, {K_HIDQT, q1.W2, TC_Q1 + LQ_W2T, 4},
-                       {K_FIRST, q2.W1, TC_Q2 + LQ_W1, 4}, {K_HIDQ, q2.W2, TC_Q2 + LQ_W2, 4}, {K_ACTIN, q2.W2, TC_Q2 + LQ_A, 1}, {K_HIDQT, q2.W2, TC_Q2 + LQ_W2T, 4}};
+    const Grp g[17] = {{K_FIRST, pi.W1, TC_PI + S::LA_W1, NQ1}, {K_HID, pi.W2, TC_PI + S::LA_W2, 4}, {KOUT, pi.W3, TC_PI + S::LA_W3, 4},
+                       {K_FIRST, tq1.W1, TC_T1 + S::LQ_W1, NQ1}, {K_HIDQ, tq1.W2, TC_T1 + S::LQ_W2, 4}, {K_ACTIN, tq1.W2, TC_T1 + S::LQ_A, NQA},
+                       {K_FIRST, tq2.W1, TC_T2 + S::LQ_W1, NQ1}, {K_HIDQ, tq2.W2, TC_T2 + S::LQ_W2, 4}, {K_ACTIN, tq2.W2, TC_T2 + S::LQ_A, NQA},
+                       {K_FIRST, q1.W1, TC_Q1 + S::LQ_W1, NQ1}, {K_HIDQ, q1.W2, TC_Q1 + S::LQ_W2, 4}, {K_ACTIN, q1.W2, TC_Q1 + S::LQ_A, NQA},
+                       {K_HIDQT, q1.W2, TC_Q1 + S::LQ_W2T, 4},
+                       {K_FIRST, q2.W1, TC_Q2 + S::LQ_W1, NQ1}, {K_HIDQ, q2.W2, TC_Q2 + S::LQ_W2, 4}, {K_ACTIN, q2.W2, TC_Q2 + S::LQ_A, NQA},
+                       {K_HIDQT, q2.W2, TC_Q2 + S::LQ_W2T, 4}};
     fill_images<D, A>(wimg, g, wave, lane);
   }
   const float b3t1 = tq1.b3[0], b3t2 = tq2.b3[0], b3q1 = q1.b3[0], b3q2 = q2.b3[0];
   __syncthreads();
   float* t0 = tilemem + (wave * 2) * 32 * TP;
   float* t1 = t0 + 32 * TP;
-  CriticAcc acc1, acc2;
+  CriticAcc<S::NB1> acc1, acc2;
   zero(acc1); zero(acc2);
   const int ntiles = (n + 31) / 32;
   for (int tl = blockIdx.x * WAVES + wave; tl < ntiles; tl += gridDim.x * WAVES) {
     Tile<D, A> t;
     gather<true>(pool, idx, n, tl, c, h, t);
-    float en[4];
-    action_quad<A>(eps_next, t.smp, t.valid, h, en);
+    float en[S::NS];
+    action_slots<A>(eps_next, t.smp, t.valid, h, en);
     float y;
     {
       v16f u1, u2;
-      float an[4], w3[16];
+      float an[S::NS], w3[16];
       const float sub = target(wimg, sbias, t.xn, en, lane, h, an);
       w3_row(sbias[5], h, w3);
-      const float qt1 = critic_forward<KS1>(wimg, TC_T1, sbias + 3, w3, b3t1, t.xn, an, lane, h, u1, u2);
+      const float qt1 = critic_forward<D, A>(wimg, TC_T1, sbias + 3, w3, b3t1, t.xn, an, lane, h, u1, u2);
       w3_row(sbias[8], h, w3);
-      const float qt2 = critic_forward<KS1>(wimg, TC_T2, sbias + 6, w3, b3t2, t.xn, an, lane, h, u1, u2);
+      const float qt2 = critic_forward<D, A>(wimg, TC_T2, sbias + 6, w3, b3t2, t.xn, an, lane, h, u1, u2);
       y = t.rew + t.live * gamma * (fminf(qt1, qt2) - sub);
     }
     critic_step(wimg, TC_Q1, sbias + 9, b3q1, t, y, lane, c, h, t0, t1, acc1);
@@ -300,21 +352,20 @@ __device__ __forceinline__ void twin_critic_grad(const Pool& pool, const long lo
 }
 
 // ---- the actor's reverse pass on a tile and its row of partial sums [gW1 | gb1 | gW2 | gb2 | gW3 | gb3]
-struct ActorAcc { v16f gW1, gW2, gW3; float gb2, gb3; };
-__device__ __forceinline__ void zero(ActorAcc& g) {
+template <int NB1> struct ActorAcc { v16f gW1[NB1], gW2, gW3; float gb2, gb3; };
+template <int NB1> __device__ __forceinline__ void zero(ActorAcc<NB1>& g) {
 #pragma unroll
-  for (int v = 0; v < 16; v++) { g.gW1[v] = 0.0f; g.gW2[v] = 0.0f; g.gW3[v] = 0.0f; }
+  for (int b = 0; b < NB1; b++) g.gW1[b] = zero16();
+  g.gW2 = zero16(); g.gW3 = zero16();
   g.gb2 = g.gb3 = 0.0f;
 }
-// Reverse mode from the cotangent wt on the output layer's pre-activation (image rows in registers v < 4 QUADS, the others zero; QUADS 1 for one
-// head, 2 for two): G2 = (W3' wt) o (a2 > 0), G1 = (W2' G2) o (a1 > 0) with the images at qW3T (QUADS of them) and qW2T (four), then the
+// Reverse mode from the cotangent wt on the output layer's pre-activation (image rows in registers v < 4 QUADS, the others zero; QUADS is NQA for one
+// head, NQH for two): G2 = (W3' wt) o (a2 > 0), G1 = (W2' G2) o (a1 > 0) with the images at qW3T (QUADS of them) and qW2T (four), then the
 // parameter gradients through the wavefront's LDS tiles (tu_trpo.hip's pass with the ReLU mask)
-template <int QUADS>
-__device__ __forceinline__ void actor_reverse(const float4 (*wimg)[64], int qW2T, int qW3T, const v16f& a1, const v16f& a2, const v16f& wt, const float (&xt)[16],
-                                              float* t0, float* t1, int lane, int c, int h, ActorAcc& g) {
-  v16f g2, g1;
-#pragma unroll
-  for (int v = 0; v < 16; v++) { g2[v] = 0.0f; g1[v] = 0.0f; }
+template <int QUADS, int NB1>
+__device__ __forceinline__ void actor_reverse(const float4 (*wimg)[64], int qW2T, int qW3T, const v16f& a1, const v16f& a2, const v16f& wt, const float (&xt)[NB1][16],
+                                              float* t0, float* t1, int lane, int c, int h, ActorAcc<NB1>& g) {
+  v16f g2 = zero16(), g1 = zero16();
 #pragma unroll
   for (int q = 0; q < QUADS; q++) {
     const float4 w = wimg[qW3T + q][lane];
@@ -339,7 +390,10 @@ __device__ __forceinline__ void actor_reverse(const float4 (*wimg)[64], int qW2T
   get(t0, ta_, c, h);
   wave_lds_sync();
 #pragma unroll
-  for (int s = 0; s < 16; s++) g.gW1 = TILE_MFMA(ta_[s], xt[s], g.gW1);
+  for (int s = 0; s < 16; s++) {
+#pragma unroll
+    for (int b = 0; b < NB1; b++) g.gW1[b] = TILE_MFMA(ta_[s], xt[b][s], g.gW1[b]);
+  }
   put(t0, wt, c, h); put(t1, a2, c, h);
   wave_lds_sync();
   get(t0, ta_, c, h); get(t1, tb_, c, h);
@@ -348,14 +402,13 @@ __device__ __forceinline__ void actor_reverse(const float4 (*wimg)[64], int qW2T
   for (int s = 0; s < 16; s++) { g.gW3 = TILE_MFMA(ta_[s], tb_[s], g.gW3); g.gb3 += ta_[s]; }
 }
 // this wavefront's row of an actor into LDS; S is the row's shape (D observations, an output layer of Kind KOUT)
-template <class S, int D, int A, int KOUT> __device__ __forceinline__ void actor_row(ActorAcc& g, float* red, int c, int h) {
+template <class S, int D, int A, int KOUT> __device__ __forceinline__ void actor_row(ActorAcc<S::NB1>& g, float* red, int c, int h) {
   g.gb2 += __shfl_xor(g.gb2, 32, 64); g.gb3 += __shfl_xor(g.gb3, 32, 64);
 #pragma unroll
   for (int v = 0; v < 16; v++) {
     const int r = row_of(v, h), o = out_row<A, KOUT>(r);
     red[S::A_W2 + r * H + c] = g.gW2[v];
-    if (c < D) red[S::A_W1 + r * D + c] = g.gW1[v];
-    if (c == D) red[S::A_B1 + r] = g.gW1[v];
+    first_layer_row<D>(g.gW1, v, r, red + S::A_W1, red + S::A_B1, c);
     if (o >= 0) red[S::A_W3 + o * H + c] = g.gW3[v];
   }
   if (h == 0) red[S::A_B2 + c] = g.gb2;
@@ -364,23 +417,24 @@ template <class S, int D, int A, int KOUT> __device__ __forceinline__ void actor
 
 // ---- the sampler's policy step: tu_trpo.hip's policy_step_mfma_kernel with ReLU hidden units.  One tile per wavefront; the float32 copy of the
 // observation goes into the pool's row obs32, the action into act and, mapped to the environment's range [low, high], into env_act (obs32 and
-// act are the pool's rows [top, top + n): the caller passes the offset pointers).  The output layer's image is of Kind KOUT;
-// head(z3, v, o, smp) gives component a = v + 4 h of sample smp's action in [-1, 1] from the pre-activation z3 (o = smp A + a).
+// act are the pool's rows [top, top + n): the caller passes the offset pointers; rows past n are not touched).  The output layer's image is of
+// Kind KOUT; head(z3, v, o, smp) gives the action component of slot v, a = row_of(v, h), of sample smp in [-1, 1] from the pre-activation z3
+// (o = smp A + a).
 template <int D, int A, int KOUT, class Head>
 __device__ __forceinline__ void policy_step(const double* __restrict__ obs, int n, const Net& th, const double* __restrict__ low, const double* __restrict__ high,
                                             float* __restrict__ obs32, float* __restrict__ act, double* __restrict__ env_act, Head head) {
-  constexpr int KS1 = (D + 1) / 2;
+  constexpr int KS1 = Shape<D, A>::KS1, NS = Shape<D, A>::NS;
   __shared__ alignas(16) float sbias[3][32];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, h = lane >> 5;
   if (tid < 32) { sbias[0][tid] = th.b1[tid]; sbias[1][tid] = th.b2[tid]; sbias[2][tid] = out_bias<A, KOUT>(th.b3, tid); }
   float aW1[KS1], aW2[16], aW3[16];
-  double lo[4], hi[4];
+  double lo[NS], hi[NS];
 #pragma unroll
   for (int s = 0; s < KS1; s++) aW1[s] = wel<D, A>(K_FIRST, th.W1, s, c, h);
 #pragma unroll
   for (int v = 0; v < 16; v++) { aW2[v] = wel<D, A>(K_HID, th.W2, v, c, h); aW3[v] = wel<D, A>(KOUT, th.W3, v, c, h); }
 #pragma unroll
-  for (int v = 0; v < 4; v++) { const int a = v + 4 * h; lo[v] = a < A ? low[a] : 0.0; hi[v] = a < A ? high[a] : 0.0; }
+  for (int v = 0; v < NS; v++) { const int a = row_of(v, h); lo[v] = a < A ? low[a] : 0.0; hi[v] = a < A ? high[a] : 0.0; }
   __syncthreads();
   const int tl = blockIdx.x * WAVES + wave;   // one tile per wavefront
   const int smp = tl * 32 + c;
@@ -405,8 +459,8 @@ __device__ __forceinline__ void policy_step(const double* __restrict__ obs, int 
 #pragma unroll
   for (int v = 0; v < 16; v++) z3 = TILE_MFMA(aW3[v], h2[v], z3);
 #pragma unroll
-  for (int v = 0; v < 4; v++) {
-    const int a = v + 4 * h;
+  for (int v = 0; v < NS; v++) {
+    const int a = row_of(v, h);
     if (valid && a < A) {
       const size_t o = (size_t)smp * A + a;
       const float val = head(z3, v, o, smp);
@@ -418,8 +472,8 @@ __device__ __forceinline__ void policy_step(const double* __restrict__ obs, int 
   }
 }
 
-// ---- Adam step and soft target update on rows of partial sums (tu_ddpg.hip's apply_kernel, tu_td3.hip's critic_apply_kernel; tu_sac.hip's
-// apply_kernel takes the pieces)
+// ---- Adam step and soft target update on rows of partial sums (tu_ddpg.hip's apply_kernel, tu_td3.hip's critic_apply_kernel; sac_kernels.h's
+// actor_apply_rows takes the pieces)
 struct Offsets { int o[7]; };   // starts of W1, b1, W2, b2, W3, b3 in the row [W1 | b1 | W2 | b2 | W3 | b3], and the parameter count
 // Every product of the three functions below is rounded (contraction off): left to the compiler, which multiply-adds are fused follows the code
 // around them, and the kernels have to give the same bits as each other (CassieTd3CriticApply is CassieDdpgApply bit for bit).

@@ -39,13 +39,13 @@ using namespace cassie_mlp32;   // shapes, operand images, tile helpers (shared 
 // ---------------------------------------------------------------------------------------------------------------- critic gradient
 // Per sample b of the batch (pool row i = idx[b]):  y = r_i + (1 - terminal_i) gamma Q'(s'_i, mu'(s'_i)),  e = Q(s_i, a_i) - y, and the
 // gradient of sum_b e^2 with respect to the live critic.  Row: [gW1 | gb1 | gW2 | gb2 | gW3 | gb3 | sum e^2 | sum Q].
-enum { CQ_TA = 0, CQ_TQ = LA_N, CQ_Q = CQ_TQ + LQ_FWD, CQ_N = CQ_Q + LQ_N };
 template <int D, int A>
 __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, const long long* __restrict__ idx, int n, Net ta, Net tq, Net q, float gamma,
                                                                     float* __restrict__ partial) {
   typedef Shape<D, A> S;
-  static_assert(D < 32 && A <= 8, "a column of ones next to the observations; the action rows in registers 0..3 of the two lane halves");
-  constexpr int KS1 = (D + 1) / 2, NROW = S::NPQ + 2;
+  static_assert(S::NS == 4, "this unit's target action and cotangent are written for four slots, the action a = v + 4 h in register v < 4 (A <= 8)");
+  enum { CQ_TA = 0, CQ_TQ = S::LA_N, CQ_Q = CQ_TQ + S::LQ_FWD, CQ_N = CQ_Q + S::LQ_N };
+  constexpr int NROW = S::NPQ + 2, NQ1 = S::NQ1;
   static_assert(WAVES * NROW <= WAVES * 2 * 32 * TP, "the workgroup's reduction re-uses the transpose tiles");
   __shared__ alignas(16) float tilemem[WAVES * 2 * 32 * TP];
   __shared__ alignas(16) float sbias[8][32];   // target actor b1 b2 b3;  target critic b1 b2 (its W3 in registers);  live critic b1 b2 W3
@@ -57,9 +57,10 @@ __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, c
     sbias[5][tid] = q.b1[tid]; sbias[6][tid] = q.b2[tid]; sbias[7][tid] = q.W3[tid];
   }
   {
-    const Grp g[10] = {{K_FIRST, ta.W1, CQ_TA + LA_W1, 4}, {K_HID, ta.W2, CQ_TA + LA_W2, 4}, {K_OUT, ta.W3, CQ_TA + LA_W3, 4},
-                       {K_FIRST, tq.W1, CQ_TQ + LQ_W1, 4}, {K_HIDQ, tq.W2, CQ_TQ + LQ_W2, 4}, {K_ACTIN, tq.W2, CQ_TQ + LQ_A, 1},
-                       {K_FIRST, q.W1, CQ_Q + LQ_W1, 4}, {K_HIDQ, q.W2, CQ_Q + LQ_W2, 4}, {K_ACTIN, q.W2, CQ_Q + LQ_A, 1}, {K_HIDQT, q.W2, CQ_Q + LQ_W2T, 4}};
+    const Grp g[10] = {{K_FIRST, ta.W1, CQ_TA + S::LA_W1, NQ1}, {K_HID, ta.W2, CQ_TA + S::LA_W2, 4}, {K_OUT, ta.W3, CQ_TA + S::LA_W3, 4},
+                       {K_FIRST, tq.W1, CQ_TQ + S::LQ_W1, NQ1}, {K_HIDQ, tq.W2, CQ_TQ + S::LQ_W2, 4}, {K_ACTIN, tq.W2, CQ_TQ + S::LQ_A, S::NQA},
+                       {K_FIRST, q.W1, CQ_Q + S::LQ_W1, NQ1}, {K_HIDQ, q.W2, CQ_Q + S::LQ_W2, 4}, {K_ACTIN, q.W2, CQ_Q + S::LQ_A, S::NQA},
+                       {K_HIDQT, q.W2, CQ_Q + S::LQ_W2T, 4}};
     fill_images<D, A>(wimg, g, wave, lane);
   }
   float w3t[16];   // in registers: read from a row of sbias like the live critic's, the kernel takes 228 + 52 registers, not 186 + 48, and occupancy 1
@@ -69,7 +70,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, c
   __syncthreads();
   float* t0 = tilemem + (wave * 2) * 32 * TP;
   float* t1 = t0 + 32 * TP;
-  CriticAcc acc;
+  CriticAcc<S::NB1> acc;
   zero(acc);
   const int ntiles = (n + 31) / 32;
   for (int tl = blockIdx.x * WAVES + wave; tl < ntiles; tl += gridDim.x * WAVES) {
@@ -80,10 +81,10 @@ __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, c
     {
       v16f a1, a2, mu, u1, u2;
       float mt[4];
-      actor_forward<KS1>(wimg, CQ_TA, sbias, t.xn, lane, h, a1, a2, mu);
+      actor_forward<D, A>(wimg, CQ_TA, sbias, t.xn, lane, h, a1, a2, mu);
 #pragma unroll
       for (int v = 0; v < 4; v++) mt[v] = tanh_fast(mu[v]);   // rows a >= A: W3 and b3 padded with zeros -> tanh(0) = 0
-      y = t.rew + t.live * gamma * critic_forward<KS1>(wimg, CQ_TQ, sbias + 3, w3t, b3t, t.xn, mt, lane, h, u1, u2);
+      y = t.rew + t.live * gamma * critic_forward<D, A>(wimg, CQ_TQ, sbias + 3, w3t, b3t, t.xn, mt, lane, h, u1, u2);
     }
     critic_step(wimg, CQ_Q, sbias + 5, b3q, t, y, lane, c, h, t0, t1, acc);   // the live critic at (s, a)
   }
@@ -96,12 +97,12 @@ __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, c
 
 // ---------------------------------------------------------------------------------------------------------------- actor gradient
 // Gradient of -sum_b Q(s_b, mu(s_b)) with respect to the actor, through the live critic.  Row: [gW1 | gb1 | gW2 | gb2 | gW3 | gb3 | sum Q].
-enum { AG_PI = 0, AG_W2T = LA_N, AG_W3T = 16, AG_Q = 17, AG_Q_DA = AG_Q + LQ_FWD, AG_N = AG_Q_DA + 4 };
 template <int D, int A>
 __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, const long long* __restrict__ idx, int n, Net th, Net q, float* __restrict__ partial) {
   typedef Shape<D, A> S;
-  static_assert(D < 32 && A <= 8, "see critic_grad_kernel");
-  constexpr int KS1 = (D + 1) / 2, NROW = S::NPA + 1;
+  static_assert(S::NS == 4, "see critic_grad_kernel");
+  enum { AG_PI = 0, AG_W2T = S::LA_N, AG_W3T = AG_W2T + 4, AG_Q = AG_W3T + S::NQA, AG_Q_DA = AG_Q + S::LQ_FWD, AG_N = AG_Q_DA + 4 };
+  constexpr int NROW = S::NPA + 1, NQ1 = S::NQ1;
   static_assert(WAVES * NROW <= WAVES * 2 * 32 * TP, "the workgroup's reduction re-uses the transpose tiles");
   __shared__ alignas(16) float tilemem[WAVES * 2 * 32 * TP];
   __shared__ alignas(16) float sbias[5][32];   // actor b1 b2 b3, critic b1 b2 (its W3 stays in registers: the LDS of this kernel is full)
@@ -112,9 +113,9 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
     sbias[3][tid] = q.b1[tid]; sbias[4][tid] = q.b2[tid];
   }
   {
-    const Grp g[9] = {{K_FIRST, th.W1, AG_PI + LA_W1, 4}, {K_HID, th.W2, AG_PI + LA_W2, 4}, {K_OUT, th.W3, AG_PI + LA_W3, 4}, {K_HIDT, th.W2, AG_W2T, 4},
-                      {K_W3T, th.W3, AG_W3T, 1}, {K_FIRST, q.W1, AG_Q + LQ_W1, 4}, {K_HIDQ, q.W2, AG_Q + LQ_W2, 4}, {K_ACTIN, q.W2, AG_Q + LQ_A, 1},
-                      {K_DA, q.W2, AG_Q_DA, 4}};
+    const Grp g[9] = {{K_FIRST, th.W1, AG_PI + S::LA_W1, NQ1}, {K_HID, th.W2, AG_PI + S::LA_W2, 4}, {K_OUT, th.W3, AG_PI + S::LA_W3, 4},
+                      {K_HIDT, th.W2, AG_W2T, 4}, {K_W3T, th.W3, AG_W3T, S::NQA}, {K_FIRST, q.W1, AG_Q + S::LQ_W1, NQ1}, {K_HIDQ, q.W2, AG_Q + S::LQ_W2, 4},
+                      {K_ACTIN, q.W2, AG_Q + S::LQ_A, S::NQA}, {K_DA, q.W2, AG_Q_DA, 4}};
     fill_images<D, A>(wimg, g, wave, lane);
   }
   float w3q[16];
@@ -124,7 +125,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
   __syncthreads();
   float* t0 = tilemem + (wave * 2) * 32 * TP;
   float* t1 = t0 + 32 * TP;
-  ActorAcc acc;
+  ActorAcc<S::NB1> acc;
   zero(acc);
   float sq = 0.0f;
   const int ntiles = (n + 31) / 32;
@@ -134,12 +135,12 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
     // ---- actor forward: mu(s), action a = v + 4 h in register v < 4
     v16f a1, a2, z3;
     float aw[16], mu[4];
-    actor_forward<KS1>(wimg, AG_PI, sbias, t.xb, lane, h, a1, a2, z3);
+    actor_forward<D, A>(wimg, AG_PI, sbias, t.xb, lane, h, a1, a2, z3);
 #pragma unroll
     for (int v = 0; v < 4; v++) mu[v] = tanh_fast(z3[v]);
     // ---- critic at (s, mu(s)) and dQ/da = W2a' (W3 o (h2 > 0))
     v16f c1, c2, da;
-    const float qv = critic_forward<KS1>(wimg, AG_Q, sbias + 3, w3q, b3q, t.xb, mu, lane, h, c1, c2);
+    const float qv = critic_forward<D, A>(wimg, AG_Q, sbias + 3, w3q, b3q, t.xb, mu, lane, h, c1, c2);
     if (h == 0 && t.valid) sq += qv;
 #pragma unroll
     for (int v = 0; v < 16; v++) da[v] = 0.0f;
@@ -152,7 +153,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) actor_grad_kernel(Pool pool, co
     for (int v = 0; v < 16; v++) wt[v] = 0.0f;
 #pragma unroll
     for (int v = 0; v < 4; v++) wt[v] = (t.valid && v + 4 * h < A) ? -da[v] * (1.0f - mu[v] * mu[v]) : 0.0f;
-    actor_reverse<1>(wimg, AG_W2T, AG_W3T, a1, a2, wt, t.xt, t0, t1, lane, c, h, acc);
+    actor_reverse<S::NQA>(wimg, AG_W2T, AG_W3T, a1, a2, wt, t.xt, t0, t1, lane, c, h, acc);
   }
 #pragma unroll
   for (int m = 16; m >= 1; m >>= 1) sq += __shfl_xor(sq, m, 64);

@@ -27,9 +27,11 @@ template <int D, int A>
 __global__ void __launch_bounds__(64 * WAVES, 1) critic_grad_kernel(Pool pool, const long long* __restrict__ idx, int n, Net ta, Net tq1, Net tq2, Net q1, Net q2,
                                                                     const float* __restrict__ eps_next, float policy_noise, float noise_clip, float gamma,
                                                                     float* __restrict__ partial) {
-  const auto target = [=](const float4 (*wimg)[64], const float (*sb)[32], const float (&xn)[(D + 1) / 2], const float (&en)[4], int lane, int h, float (&an)[4]) {
+  typedef Shape<D, A> S;
+  static_assert(S::NS == 4, "the target action below is written for four slots, the action a = v + 4 h in register v < 4 (A <= 8)");
+  const auto target = [=](const float4 (*wimg)[64], const float (*sb)[32], const float (&xn)[S::KS1], const float (&en)[4], int lane, int h, float (&an)[4]) {
     v16f a1, a2, mu;
-    actor_forward(wimg, TC_PI, sb, xn, lane, h, a1, a2, mu);
+    actor_forward<D, A>(wimg, TC_PI, sb, xn, lane, h, a1, a2, mu);
 #pragma unroll
     for (int v = 0; v < 4; v++)   // rows a >= A: W3, b3 and the noise are zeros -> a' = 0, on zero columns of the merge layer's image
       an[v] = clip(tanh_fast(mu[v]) + clip(policy_noise * en[v], -noise_clip, noise_clip), -1.0f, 1.0f);

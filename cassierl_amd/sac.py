@@ -35,9 +35,10 @@ launches.  Each has its torch statement in this module (SquashedGaussianMLPPolic
 library without the entry points run those.
 
 On Cassie3d (make_cassie_sac(n, env="cassie3d", control_mode="PD" | "Torque", kp=.., kd=..): 45 observations, 10 actions, the standing reset) the
-same 32 x 32 networks run on the kernels of csrc/tu_sac3d.hip -- CassieSac3dPolicyStep, CassieSac3dCriticGrad, CassieSac3dCriticApply for each critic,
-CassieSac3dActorGrad, CassieSac3dActorApply, still five launches per update -- and everything above holds unchanged: target_entropy defaults to -10,
-and a pool row is 4 (2 D + A + 2) = 408 bytes, so the default pool of 1 000 000 rows is 408 MB per rank.
+same 32 x 32 networks run on the same kernels (csrc/sac_kernels.h, instantiated at <45, 10> by csrc/tu_sac3d.hip) -- CassieSac3dPolicyStep,
+CassieSac3dCriticGrad, CassieSac3dCriticApply for each critic, CassieSac3dActorGrad, CassieSac3dActorApply, still five launches per update -- and
+everything above holds unchanged: target_entropy defaults to -10, and a pool row is 4 (2 D + A + 2) = 408 bytes, so the default pool of
+1 000 000 rows is 408 MB per rank.
 """
 import ctypes as ct
 import math
@@ -120,7 +121,7 @@ def sac_update_torch_(actor, qf1, qf2, target_qf1, target_qf2, log_alpha, adam_p
     return losses[0], losses[1], policy_loss.detach(), avg_logp, alpha.reshape(())
 
 
-SHAPE3D = (45, 10)   # Cassie3d: the kernels of csrc/tu_sac3d.hip
+SHAPE3D = (45, 10)   # Cassie3d: the entry points of csrc/tu_sac3d.hip
 
 
 def kernels_cover(actor, qf1, qf2):

@@ -334,7 +334,7 @@ int CassieVfGradRows(int m);
 int CassieVfGrad(const float* obs_dev, int n, int obs_dim, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
                  const float* b3, const long long* idx_dev, int m, const float* target_dev, float scale, float* partial_dev, double* stats_dev, void* stream);
 
-/* ---- SAC at 45 x 10: Soft Actor-Critic on Cassie3d (cassierl_amd/sac.py with env="cassie3d", csrc/tu_sac3d.hip, csrc/mlp32_tiles3d.h).  The networks
+/* ---- SAC at 45 x 10: Soft Actor-Critic on Cassie3d (cassierl_amd/sac.py with env="cassie3d", csrc/tu_sac3d.hip on the kernels of csrc/sac_kernels.h).  The networks
  * are still the 32 x 32 ReLU networks above: the actor's W1 [32][45], W3 [20][32] (mean rows [0, 10), log_std rows [10, 20)), a critic's W1 [32][45],
  * W2 [32][42].  The contracts of CassieSacPolicyStep, CassieSacCriticGrad, CassieSacActorGrad and CassieSacApply (here CassieSac3dActorApply) for the
  * one shape obs_dim = 45, act_dim = 10; any other shape, a null pointer, batch / n / rows <= 0 or a misaligned pointer is CASSIE_EINVAL before

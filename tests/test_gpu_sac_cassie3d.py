@@ -1,4 +1,4 @@
-"""SAC at the Cassie3d shape, 45 observations and 10 actions (csrc/tu_sac3d.hip, csrc/mlp32_tiles3d.h): the six CassieSac3d* entry points against the
+"""SAC at the Cassie3d shape, 45 observations and 10 actions (csrc/tu_sac3d.hip on the shape-generic kernels of csrc/sac_kernels.h and csrc/mlp32_tiles.h): the six CassieSac3d* entry points against the
 torch statements of cassierl_amd/sac.py, the whole update and the resume on Cassie3dVecEnv, train_sac.py --env cassie3d and sim_policy.py.  -m gpu only.
 
 Networks, pool and bounds are tests/test_gpu_sac.py's; the gradient bound is applied per parameter block, relative to the block's own largest entry,

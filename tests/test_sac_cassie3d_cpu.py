@@ -1,5 +1,5 @@
 """SAC on Cassie3d, the parts that need no GPU: the builder's refusals (raised before any device is touched), which shapes the kernels cover, the
-environment family in snapshots, the torch statement of the update at 45 x 10, and the library's CassieSac3d* exports."""
+environment family in snapshots, the torch statement of the update at 45 x 10, and the library's CassieSac3d* exports (csrc/tu_sac3d.hip, a unit of its own on the shape-generic kernels of csrc/sac_kernels.h)."""
 import ctypes as ct
 
 import pytest

@@ -1,15 +1,16 @@
 #!/usr/bin/env python3
-"""Bit-for-bit A/B of the off-policy units (csrc/tu_ddpg.hip, tu_sac.hip, tu_td3.hip) between two builds of the library (not a test), in the manner
-of tools/ab_onpolicy_bits.py, whose helpers it uses: every entry point of the three units is called with fixed-seed inputs and one line
+"""Bit-for-bit A/B of the off-policy units (csrc/tu_ddpg.hip, tu_sac.hip, tu_sac3d.hip, tu_td3.hip) between two builds of the library (not a test), in the manner
+of tools/ab_onpolicy_bits.py, whose helpers it uses: every entry point of the four units is called with fixed-seed inputs and one line
 `<case> <buffer> <sha256 of the buffer's bytes>` is printed per output buffer.  Run once per library, each in its own process (CASSIE2D_LIB selects
 the library), and diff the outputs:
     python tools/ab_offpolicy_bits.py > a.txt;  CASSIE2D_LIB=/path/to/other/libcassie2d.so python tools/ab_offpolicy_bits.py > b.txt;  diff a.txt b.txt
 Batches: 1, 31, 33, 129, 1000, and 32 768 + 33 for the gradients (past the grid cap of 256 workgroups: the tile loop takes a second trip), 65 536 + 33
 for the policy steps and the pool commit; all four (obs_dim, act_dim) pairs where the entry point has them.  The batch's index holds entries out of the
 pool's range (clamped), outputs are pre-filled with NaN, and every apply kernel takes the partial rows of the gradient call before it (1, 2, 8 and 256
-rows).  CassieSacApply runs with and without a temperature state.
+rows).  CassieSacApply runs with and without a temperature state.  The six CassieSac3d* entry points run at (45, 10) in the same manner: both
+critics' CassieSac3dCriticApply on their blocks of the gradient call's rows, CassieSac3dActorApply with and without a temperature state.
     python tools/ab_offpolicy_bits.py --time [reps]
-times the three policy steps instead (65 536 rows, median of `reps` synchronised calls): one JSON line per entry point."""
+times the four policy steps instead (65 536 rows, median of `reps` synchronised calls): one JSON line per entry point."""
 import ctypes as ct
 import json
 import os
@@ -104,8 +105,61 @@ def run_updates():
             emit(tag + " td3 criticapply", qf1=flat(l1), qf2=flat(l2), target1=flat(t1), target2=flat(t2), m1=ms[0], v1=vs[0], m2=ms[1], v2=vs[1], stats=stats)
 
 
-def step_inputs(A, n):
-    D = 26
+def run_sac3d():
+    D, A = 45, 10
+    NPA, NPQ = L.CassieSac3dParamCount(D, A, ACTOR), L.CassieSac3dParamCount(D, A, CRITIC)
+    for n in SIZES + [GRAD_CAP]:
+        GEN.manual_seed(7000 * D + 70 * A + n % 997)
+        tag = "D%d A%d n%d" % (D, A, n)
+        cap = n + 77
+        obs, nobs, act = rnd(cap, D, scale=0.7), rnd(cap, D, scale=0.7), rnd(cap, A).tanh()
+        rew, term = rnd(cap, scale=0.1), (torch.rand(cap, generator=GEN) < 0.1).float().to(DEV)
+        idx = torch.randint(-2, cap + 2, (n,), generator=GEN, dtype=torch.int64).to(DEV)
+        eps, eps_next, log_alpha = rnd(n, A), rnd(n, A), rnd(1, scale=0.5)
+        pi2 = net(D, 2 * A, 32)
+        q1, q2, tq1, tq2 = critic(D, A), critic(D, A), critic(D, A), critic(D, A)
+        rows = L.CassieDdpgPartialRows(n)
+        # both critics' gradient, each critic's apply on its block of the rows
+        part = nan_like(2, rows, NPQ + 2)
+        call("CassieSac3dCriticGrad", P(obs), P(act), P(rew), P(term), P(nobs), ct.c_longlong(cap), P(idx), n, D, A, N(pi2), N(tq1), N(tq2), N(q1), N(q2), P(eps_next),
+             P(log_alpha), F(0.99), P(part))
+        emit(tag + " sac3d criticgrad", partial=part)
+        for k, (q, tq) in enumerate(((q1, tq1), (q2, tq2))):
+            live, targ = copies(q), copies(tq)
+            m, v, stats = rnd(NPQ, scale=0.01), rnd(NPQ, scale=0.01).abs(), rnd(2, dtype=torch.float64)
+            call("CassieSac3dCriticApply", rows, D, A, P(part[k]), F(1.0 / 7), N(live), N(targ), P(m), P(v), 3, *ADAM, F(5e-3), P(stats))
+            emit(tag + " sac3d criticapply %d" % (k + 1), live=flat(live), target=flat(targ), m=m, v=v, stats=stats)
+        # actor gradient, its apply with and without a temperature state
+        part = nan_like(rows, NPA + 2)
+        call("CassieSac3dActorGrad", P(obs), ct.c_longlong(cap), P(idx), n, D, A, N(pi2), N(q1), N(q2), P(eps), P(log_alpha), P(part))
+        emit(tag + " sac3d actorgrad", partial=part)
+        for label, tuned in (("alpha", True), ("fixed", False)):
+            live, la = copies(pi2), log_alpha.clone()
+            m, v, stats = rnd(NPA, scale=0.01), rnd(NPA, scale=0.01).abs(), rnd(3, dtype=torch.float64)
+            am, av = (rnd(1, scale=0.01), rnd(1, scale=0.01).abs()) if tuned else (None, None)
+            call("CassieSac3dActorApply", rows, D, A, P(part), F(1.0 / 7), N(live), P(m), P(v), 3, *ADAM, P(la), P(am), P(av), 2 if tuned else 0, F(3e-4), F(-float(A)),
+                 P(stats))
+            bufs = dict(live=flat(live), m=m, v=v, log_alpha=la, stats=stats)
+            if tuned:
+                bufs.update(alpha_m=am, alpha_v=av)
+            emit(tag + " sac3d actorapply " + label, **bufs)
+    for n in SIZES + [STEP_CAP]:
+        GEN.manual_seed(4510 + n % 997)
+        th2, ins = net(D, 2 * A, 32), step_inputs(A, n, D)
+        args, bufs = sac3d_step(n, th2, ins)
+        call("CassieSac3dPolicyStep", *args)
+        emit("CassieSac3dPolicyStep n%d" % n, **bufs)
+
+
+def sac3d_step(n, th2, ins):
+    """CassieSac3dPolicyStep's call and its output buffers."""
+    D, A = 45, 10
+    obs64, noise, low, high = ins[:4]
+    o32, a32, env = nan_like(n, D), nan_like(n, A), nan_like(n, A, dtype=torch.float64)
+    return (P(obs64), n, D, A, N(th2), P(noise), P(low), P(high), P(o32), P(a32), P(env)), dict(obs32=o32, act=a32, env_act=env)
+
+
+def step_inputs(A, n, D=26):
     obs64, noise = rnd(n, D, dtype=torch.float64), rnd(n, A)
     low, high = -rnd(A, dtype=torch.float64).abs() - 0.5, rnd(A, dtype=torch.float64).abs() + 0.5
     path_t = torch.randint(0, 3, (n,), generator=GEN, dtype=torch.int64).to(DEV)   # a third of the paths are fresh
@@ -153,7 +207,10 @@ def time_steps(reps):
     A, n = 6, 65536
     GEN.manual_seed(9)
     th, th2 = net(26, A, 32), net(26, 2 * A, 32)
-    for name, (args, _) in policy_steps(A, n, th, th2, step_inputs(A, n)).items():
+    ins, th3d, ins3d = step_inputs(A, n), net(45, 20, 32), step_inputs(10, n, 45)   # named: the calls below hold raw pointers into them
+    steps = policy_steps(A, n, th, th2, ins)
+    steps["CassieSac3dPolicyStep"] = sac3d_step(n, th3d, ins3d)
+    for name, (args, _) in steps.items():
         ts = []
         for r in range(reps + 3):   # three warm-up rounds
             torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -171,3 +228,4 @@ if __name__ == "__main__":
         sys.exit(0)
     run_updates()
     run_steps()
+    run_sac3d()

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""A/B of SAC at the Cassie3d shape, 45 observations and 10 actions (csrc/tu_sac3d.hip; not a test).
+"""A/B of SAC at the Cassie3d shape, 45 observations and 10 actions (csrc/tu_sac3d.hip, whose kernels are csrc/sac_kernels.h's at <45, 10>; not a test).
   1. one update, the five launches against sac.sac_update_torch_, alternated in one process at batch 4096 and 65 536 on a pool of 1 048 576
      rows, as tools/ab_sac_update.py does for 26 x 6: each round warm-up, then the median of `reps` synchronised repeats per side;
   2. train_sac.py --env cassie3d --timing at 16 384 environments, batch 16 384, with and without --torch-update, each in a child process: the
      seconds of the second epoch of 8 vector steps (the first fills the pool and warms up).
-One JSON line per round, batch and side, then one per training run.
-usage: python tools/ab_sac_cassie3d.py [rounds] [reps] > profiles/sac_cassie3d_ab.jsonl"""
+One JSON line per round, batch and side, then one per training run.  With --update-only part 2 is left out (an A/B of two builds of the library,
+CASSIE2D_LIB, times part 1 in alternated processes).
+usage: python tools/ab_sac_cassie3d.py [rounds] [reps] [--update-only] > profiles/sac_cassie3d_ab.jsonl"""
 import copy
 import json
 import os
@@ -21,8 +22,10 @@ import torch  # noqa: E402
 from cassierl_amd import ddpg as G  # noqa: E402
 from cassierl_amd import sac as S  # noqa: E402
 
-rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+update_only = "--update-only" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--update-only"]
+rounds = int(argv[0]) if len(argv) > 0 else 3
+reps = int(argv[1]) if len(argv) > 1 else 20
 
 
 def med_us(fn):
@@ -58,6 +61,8 @@ for r in range(rounds):
                                                       -float(A)))]
         for side, fn in (sides if r % 2 == 0 else sides[::-1]):
             print(json.dumps(dict(what="update", round=r, batch=batch, side=side, median_us=med_us(fn))), flush=True)
+if update_only:
+    sys.exit(0)
 del pool, nets, k
 torch.cuda.empty_cache()
 n = 16384
