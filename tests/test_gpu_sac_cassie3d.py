@@ -3,7 +3,13 @@ torch statements of cassierl_amd/sac.py, the whole update and the resume on Cass
 
 Networks, pool and bounds are tests/test_gpu_sac.py's; the gradient bound is applied per parameter block, relative to the block's own largest entry,
 with the blocks cut where the kernels' layout changes: the two column blocks of W1, the third action quad of the critic's W2, the slots 8 and 9 of
-both heads of the actor's W3 / b3."""
+both heads of the actor's W3 / b3.
+
+The hard cases of the gradient kernels and of the policy step at this shape live in tests/test_gpu_offpolicy_edges_cassie3d.py, on
+tests/test_gpu_offpolicy_edges.py's method: batches from 1 to 256 and 4099, the log_std clamp on some and on every component, saturated actions, tied
+critics, wild rows and the policy step with the wide head, every gradient block (the cuts of _blocks below, column 44 of W1 on its own) against
+FLOAT64 autograd, for the critics too.  This file keeps the large batches (up to 32 801), the apply entries (1 to 256 partial rows), the
+refusals, the whole update, the resume, the scripts and the timing."""
 import copy
 import ctypes as ct
 import functools
@@ -235,10 +241,11 @@ def test_gradients_with_the_clamp_active():
 
 
 # ------------------------------------------------------------------------------------------------------------------ apply
-@pytest.mark.parametrize("rows", [1, 64])
+@pytest.mark.parametrize("rows", [1, 2, 64, 256])
 @pytest.mark.parametrize("learn_alpha", [True, False])
 def test_apply_matches_adam_and_the_log_alpha_step(learn_alpha, rows):
-    """Five steps with gradients spanning 1e-4 .. 1: CassieSac3dActorApply (actor, log_alpha) and CassieSac3dCriticApply (Adam + soft update)."""
+    """Five steps with gradients spanning 1e-4 .. 1: CassieSac3dActorApply (actor, log_alpha) and CassieSac3dCriticApply (Adam + soft update).
+    rows: 2 takes column_sum's tail loop alone, 64 its groups of eight alone, 256 is MAX_BLOCKS, the most partial rows a gradient launch writes."""
     import torch
     from cassierl_amd import ddpg as G
     from cassierl_amd import sac as S
